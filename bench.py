@@ -5,16 +5,19 @@ Workload (BASELINE.json configs[1]): one clip per GPU, 30 frames, 256x256 silhou
 bottle, full step-1 loss set, Adam step included.  A "step" = one optimisation iteration (forward + backward +
 Adam + loss logging) of one clip, replayed from a hipGraph.  N GPUs = N independent clips (weak scaling, no
 data-path collective).  Prints ONE JSON line (<= 2 KB) on rank 0 - the LAST line of
-stdout - with the contract's keys plus
+stdout - with the contract's keys (`ms_per_step` = milliseconds of one timed step) plus
+  ranks / per_rank_its   what the process group reports and every rank's own rate (N > 1).
+A plain run sets up, warms up (--warmup), times --steps iterations, writes the outputs of the last timed step when
+--dump-outputs DIR is given, and prints the line.  With --full it also measures, after the headline:
   roofline          the dominant kernel timed INSIDE the replayed graph (device wall-clock stamps, hm_sil_timestamps), its
                     algorithmic bytes / that time / 8 TB/s (live); `traffic` / `valu_frac` from the committed PMC passes
                     under profiles/ (tools/pmc_loop.sh) when they were measured on the same shapes (`traffic_source` says so);
   cpu_baseline      the oracle loop timed on this host (bounded sample, rank 0 at N = 1 only);
   steady_state      one number: the same fit past iteration 400;
   multi_clip        one number: BASELINE cfg4 in miniature, `--multi-clip` clips per GPU as ONE clip batch;
-  ranks / per_rank_its   what the process group reports and every rank's own rate (N > 1).
-Everything else (per-kernel tables, notes, and with `--parity` the HIP-vs-oracle legs of bench_parity.py) goes to
-gpurun_out/bench_detail.json and stderr.  The default run finishes in about a minute.
+  cfg2_depth / cfg3 one number each: the --legs.
+Everything else (per-kernel tables, notes, and with `--parity` (implies --full) the HIP-vs-oracle legs of bench_parity.py)
+goes to the detail file ($HOMAN_BENCH_DETAIL) and stderr.  The --full run finishes in about a minute.
 """
 import argparse
 import copy
@@ -160,13 +163,18 @@ def bench_shared_scale(args, rank, world, backend, mano, sil_fn, hand_fn):
     elapsed = hdist.max_over_ranks(time.perf_counter() - t0, device="cuda" if backend == "nccl" else "cpu")
     evo = st.loss_evolution(total)
     evo = evo if isinstance(evo, list) else [evo]
+    if args.dump_outputs and rank == 0:
+        out = {}
+        for ci, e in enumerate(evo):
+            out.update({f"clip{ci}_{k}": v for k, v in step_outputs(models[ci], e, total - 1).items()})
+        dump_outputs(args.dump_outputs, out)
     scale = st.model.int_scales_object.detach().reshape(-1)
     wire = scale[:1].contiguous() if backend == "nccl" else scale[:1].cpu()       # (gloo moves host memory)
     gathered = [torch.zeros_like(wire) for _ in range(world)]
     dist.all_gather(gathered, wire)
     same = bool((scale == scale[0]).all()) and all(torch.equal(g, gathered[0]) for g in gathered)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the same tied-scale semantics as a plain autograd loop over the CPU oracle (homan_amd.dist.optimize_clips_shared_scale,
         # the loop the gloo tests drive), on a bounded sample: two of the clips, a few iterations
         from oracle.jointopt import collate_inputs, make_optimizer
@@ -216,7 +224,7 @@ def pose_init_bench(args):
     import torch
     from homan_amd import pose_optimization as po
     from homan_amd import synth
-    n, size, steps = args.pose_init, args.size, (50 if args.steps == 400 else args.steps)
+    n, size, steps = args.pose_init, args.size, args.steps
     ov, of = synth.bottle_mesh()
     verts, faces = torch.from_numpy(ov), torch.from_numpy(of).long()
     K = np.array([[480.0, 0, 175.0], [0, 480.0, 175.0], [0, 0, 1.0]], np.float32)
@@ -239,12 +247,12 @@ def pose_init_bench(args):
                                                num_initializations=n, rotations_init=rots, rend_size=size, mode=mode)
     # the loops of find_optimal_pose: "eager" = the reference's loop verbatim (torch autograd + Adam, one host sync per step),
     # "graph" = that step captured in a hipGraph, "fused" (the default of find_optimal_pose) = the step as a fixed C-ABI launch
-    # sequence without the autograd tape, in a hipGraph.  The fastest is reported, all are listed.
+    # sequence without the autograd tape, in a hipGraph.  The fastest is reported, all are listed (--full; a plain run: "fused").
     loops, best, cold = {}, None, None
-    for mode in os.environ.get("HOMAN_POSEINIT_LOOPS", "eager,graph,fused").split(","):
+    for mode in os.environ.get("HOMAN_POSEINIT_LOOPS", "eager,graph,fused" if args.full else "fused").split(","):
         fit(3, mode)                               # warm-up (allocations, lazy init)
         torch.cuda.synchronize()
-        if mode == "fused":
+        if mode == "fused" and args.full:
             # the fused loop is run by a RESIDENT fitter (po.PoseFitter, one per mesh / candidate count / mask size - what the
             # per-frame fits of find_optimal_poses share): the timed fit below reuses the one the warm-up built.  A fit that
             # builds everything itself (the first frame of a clip) is timed beside it.
@@ -263,42 +271,49 @@ def pose_init_bench(args):
     el = loops[best]
     with torch.no_grad():
         _, iou, _ = model()
-    # roofline of the dominant kernel of the fused step, measured inside its replayed hipGraph (the kernels stamp the device wall
-    # clock, as for the headline): a fit of the same candidates, its last `reps` replays stamped
-    reps = 20
-    trans0 = po.TCO_init_from_boxes_zup_autodepth(bbox, torch.matmul(verts.unsqueeze(0), rots), torch.as_tensor(K)[None]).unsqueeze(1)
-    sm = po.PoseOptimizer(ref_image=mask, vertices=verts, faces=faces, rotation_init=po.matrix_to_rot6d(rots),
-                          translation_init=trans0, num_initializations=n, K=roi)
-    stamps = po._fused_loop(sm, 1e-2, max(steps - reps, 3), stamp_reps=reps)[3]
-    kb = kernel_bytes(n, size // 2, int(faces.shape[0]), noaa=True)
-    pmc = {}
-    ppath = next((p for p in (os.path.join(ROOT, "profiles", f) for f in ("r06_pmc_poseinit.json", "r05_pmc_poseinit.json", "r04_pmc_poseinit.json"))
-                  if os.path.exists(p)), None)
-    if ppath:
-        pj = json.load(open(ppath))
-        if pj.get("shape") == dict(poses=n, size=size, faces=int(faces.shape[0])):
-            pmc = pj.get("per_launch", {})
-    per = {}
-    for name, us in stamps.items():
-        rec = dict(avg_launch_us=us, algorithmic_bytes=kb[name], achieved_GBps=kb[name] / (us * 1e-6) / 1e9)
-        c = pmc.get(name, {})
-        if c.get("traffic_bytes"):
-            rec["traffic_bytes"] = c["traffic_bytes"]
-        if c.get("SQ_INSTS_VALU"):
-            rec["valu_wave_instr"] = c["SQ_INSTS_VALU"]
-            rec["valu_frac"] = c["SQ_INSTS_VALU"] / (us * 1e-6 * 1024 * 2.4e9 / 4)
-        per[name] = rec
-    dom = max(per, key=lambda k: per[k]["avg_launch_us"])
-    roof = dict(bound="hbm", kernel=dom, achieved=per[dom]["achieved_GBps"], peak=8000.0, unit="GB/s",
-                frac=per[dom]["achieved_GBps"] / 8000.0, traffic=per[dom].get("traffic_bytes"),
-                avg_launch_us=per[dom]["avg_launch_us"], kernels=per,
-                timing=f"device wall clock stored by every workgroup at entry and exit in the last {reps} replays of a "
-                       f"{steps}-step fit's hipGraph (hm_sil_timestamps) - ONE loop over all {n} candidates (po._fused_loop), its "
-                       f"launches alone on the GPU; the timed fits run through the resident fitter, which walks the candidates as "
-                       f"`candidate_groups` loops side by side (same kernels over a third of the candidates each, overlapping)",
-                traffic_source=f"profiles/{os.path.basename(ppath)} (committed rocprofv3 --pmc passes, tools/pmc_poseinit.sh)" if per[dom].get("traffic_bytes") else None)
+    if args.dump_outputs:
+        out = {"iou": iou.detach().float().cpu().numpy()}
+        for name, p in model.named_parameters():
+            out["param_" + name.replace(".", "_")] = p.detach().float().cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
+    roof = None
+    if args.full:
+        # roofline of the dominant kernel of the fused step, measured inside its replayed hipGraph (the kernels stamp the device wall
+        # clock, as for the headline): a fit of the same candidates, its last `reps` replays stamped
+        reps = 20
+        trans0 = po.TCO_init_from_boxes_zup_autodepth(bbox, torch.matmul(verts.unsqueeze(0), rots), torch.as_tensor(K)[None]).unsqueeze(1)
+        sm = po.PoseOptimizer(ref_image=mask, vertices=verts, faces=faces, rotation_init=po.matrix_to_rot6d(rots),
+                              translation_init=trans0, num_initializations=n, K=roi)
+        stamps = po._fused_loop(sm, 1e-2, max(steps - reps, 3), stamp_reps=reps)[3]
+        kb = kernel_bytes(n, size // 2, int(faces.shape[0]), noaa=True)
+        pmc = {}
+        ppath = next((p for p in (os.path.join(ROOT, "profiles", f) for f in ("r06_pmc_poseinit.json", "r05_pmc_poseinit.json", "r04_pmc_poseinit.json"))
+                      if os.path.exists(p)), None)
+        if ppath:
+            pj = json.load(open(ppath))
+            if pj.get("shape") == dict(poses=n, size=size, faces=int(faces.shape[0])):
+                pmc = pj.get("per_launch", {})
+        per = {}
+        for name, us in stamps.items():
+            rec = dict(avg_launch_us=us, algorithmic_bytes=kb[name], achieved_GBps=kb[name] / (us * 1e-6) / 1e9)
+            c = pmc.get(name, {})
+            if c.get("traffic_bytes"):
+                rec["traffic_bytes"] = c["traffic_bytes"]
+            if c.get("SQ_INSTS_VALU"):
+                rec["valu_wave_instr"] = c["SQ_INSTS_VALU"]
+                rec["valu_frac"] = c["SQ_INSTS_VALU"] / (us * 1e-6 * 1024 * 2.4e9 / 4)
+            per[name] = rec
+        dom = max(per, key=lambda k: per[k]["avg_launch_us"])
+        roof = dict(bound="hbm", kernel=dom, achieved=per[dom]["achieved_GBps"], peak=8000.0, unit="GB/s",
+                    frac=per[dom]["achieved_GBps"] / 8000.0, traffic=per[dom].get("traffic_bytes"),
+                    avg_launch_us=per[dom]["avg_launch_us"], kernels=per,
+                    timing=f"device wall clock stored by every workgroup at entry and exit in the last {reps} replays of a "
+                           f"{steps}-step fit's hipGraph (hm_sil_timestamps) - ONE loop over all {n} candidates (po._fused_loop), its "
+                           f"launches alone on the GPU; the timed fits run through the resident fitter, which walks the candidates as "
+                           f"`candidate_groups` loops side by side (same kernels over a third of the candidates each, overlapping)",
+                    traffic_source=f"profiles/{os.path.basename(ppath)} (committed rocprofv3 --pmc passes, tools/pmc_poseinit.sh)" if per[dom].get("traffic_bytes") else None)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import poseopt
         torch.set_num_threads(int(os.environ.get("OMP_NUM_THREADS", "1")))
         nc, kc = min(n, 64), 10
@@ -424,6 +439,33 @@ def emit(full):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (out + "\n").encode())
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model, evo, step):
+    """What a caller of the timed path holds after its `step`-th iteration (0-based): that iteration's loss_evolution row
+    (reference jointopt.py:184-189: every loss and metric, and the weighted total) and the model's parameters after its Adam
+    update.  `evo` is one clip's loss_evolution dict."""
+    import numpy as np
+    out = {f"evo_{k}": np.array([v[step]], np.float64) for k, v in sorted(evo.items())}
+    for name, p in model.named_parameters():
+        out["param_" + name.replace(".", "_")] = p.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 stays float64); at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs of {total} bytes exceed the {DUMP_MAX_BYTES}-byte dump"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    _leg(f"outputs: {len(arrays)} arrays, {total} bytes -> {path}")
+
+
 def _launch_ranks(n):
     """Re-executes this command under torch.distributed.run with n ranks on this node (rendezvous on 127.0.0.1, a free port);
     rank 0 of the children prints the JSON line on the inherited stdout."""
@@ -453,7 +495,8 @@ def main():
     _quiet_stdout()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed iterations (default 400; --pose-init: Adam steps of the timed fit, default 50)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--size", type=int, default=256)
@@ -492,10 +535,21 @@ def main():
     ap.add_argument("--lockstep", type=int, default=24)
     ap.add_argument("--freerun", type=int, default=100)
     ap.add_argument("--e2e-clips", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the legs that are not part of its figure: roofline stamps, steady_state, "
+                         "multi_clip, the --legs, cpu_baseline (and with --parity the parity legs).  Off: set up, warm up, time "
+                         "--steps, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (loss_evolution row, "
+                         "parameters after the Adam update) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=10.0,
                     help="seconds of CPU work of the cpu_baseline leg (rank 0, N = 1 only)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 50 if args.pose_init else 400
+    if args.parity:
+        args.full = True         # (the parity legs compare against the cpu_baseline leg's trajectory)
 
     if args.pose_init:
         assert args.gpus == 1, "--pose-init is a one-GPU line"
@@ -545,10 +599,10 @@ def main():
                         objvertices=clip["objvertices"], objfaces=clip["objfaces"], camintr=clip["camintr"],
                         optimize_mano=True, image_size=args.size, mano_model=mano, rend_size=args.size,
                         sync_metrics=False, ordinal_depth=args.depth)
-    fused = args.loop == "fused"
-    steady_warm = max(0, 400 - (args.warmup + args.steps)) if args.steady > 0 and fused else 0
+    fused, full = args.loop == "fused", args.full
+    steady_warm = max(0, 400 - (args.warmup + args.steps)) if args.steady > 0 and fused and full else 0
     stamp_reps = max(10, min(50, args.steps))
-    total_steps = args.warmup + args.steps + (2 * stamp_reps + steady_warm + args.steady if fused else 0)
+    total_steps = args.warmup + args.steps + (2 * stamp_reps + steady_warm + args.steady if fused and full else 0)
     stepper = (FusedStepper if fused else GraphStepper)(model, lw, 1e-2, total_steps)
     stepper.run(args.warmup)
 
@@ -584,6 +638,10 @@ def main():
 
     _leg(f"headline: {args.steps} timed iterations")
     elapsed = timed(args.steps, per_rank)
+    if args.dump_outputs and rank == 0:
+        # before any --full leg steps the same fit further
+        dump_outputs(args.dump_outputs, step_outputs(model, stepper.loss_evolution(args.warmup + args.steps),
+                                                     args.warmup + args.steps - 1))
     B, S = args.frames, args.size
     F, V = clip["objfaces"].shape[1], clip["objvertices"].shape[1]
 
@@ -668,7 +726,7 @@ def main():
                                          frac=tot * its_per_s / 8.0e12))
 
     roof = steady = None
-    if fused:
+    if fused and full:
         _leg("roofline stamps")
         r = stamp_roofline(args.steps / elapsed, stamp_reps) if rank == 0 else stepper.run(stamp_reps)
         roof = r if rank == 0 else None
@@ -689,7 +747,7 @@ def main():
     evo = stepper.loss_evolution(args.warmup + args.steps)
 
     multi = None
-    if args.multi_clip > 1 and args.loop == "fused":
+    if full and args.multi_clip > 1 and args.loop == "fused":
         # BASELINE config 4 in miniature: `multi_clip` independent clips per GPU as ONE clip batch (homan_amd.clipbatch):
         # every kernel is launched once per iteration over all the clips (per-clip normalisers, Adam state, log rows), the
         # whole batched iteration is one hipGraph; every rank its own set, no collective; aggregate = all clips of all
@@ -734,7 +792,7 @@ def main():
         del bst, models
 
     legs = {}
-    if fused and world == 1 and not args.step2 and not args.depth and args.legs:
+    if full and fused and world == 1 and not args.step2 and not args.depth and args.legs:
         from homan_amd import lib as hlib
         import ctypes
         for name in [x for x in args.legs.split(",") if x in LEG_KEYS]:
@@ -785,7 +843,7 @@ def main():
 
     cpu = parity = e2e = None
     parity_ok = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         _leg(f"cpu_baseline: oracle loop, {args.cpu_budget:.0f} s budget")
         cpu, evo_cpu = cpu_baseline(clip, lw, mano, args.cpu_budget, rend_size=S, image_size=S, ordinal_depth=args.depth)
         if args.parity:

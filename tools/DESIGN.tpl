@@ -322,9 +322,10 @@ next to them.  HIP-runtime and hardware facts that shaped it (all measured, EXPE
 
 ## 5. Measured (MI355X, round 6; evidence under `profiles/r06_*`, regenerated by `tools/profile_round.sh r06`)
 
-`python bench.py` prints ONE compact JSON line (<= 2 KB: the contract's keys, `roofline`, `cpu_baseline`, one number each for
+`python bench.py --full` prints ONE compact JSON line (<= 2 KB: the contract's keys, `roofline`, `cpu_baseline`, one number each for
 the `steady_state`, `multi_clip`, `cfg2_depth` and `cfg3` legs) and writes the full record - per-kernel tables, notes, with `--parity` the HIP-vs-oracle
-legs of `bench_parity.py` - to `gpurun_out/bench_detail.json` and stderr; the default run takes ~25 s on the GPU box.  (Round 4's
+legs of `bench_parity.py` - to the detail file (`$HOMAN_BENCH_DETAIL`) and stderr; that run takes ~25 s on the GPU box.  A plain
+`python bench.py` times the headline alone (set up, warm up, `--steps` timed iterations, the line with the contract's keys).  (Round 4's
 line was 23 KB, parity traces included, and came back from the driver as `parsed: null`.)  Default workload: cfg2, 400 steps
 after 20 warm-up, then - same process, same fit, same hipGraph - a `steady_state` leg (iteration >= 400, 1000 timed iterations)
 so that ONE line carries both regimes whatever `--steps / --warmup` the driver passes (it passes `--steps 20 --warmup 5`:
@@ -341,7 +342,7 @@ iterations 5-25 of a fresh fit).  `profiles/r06_bench_*.json` are the full recor
 | END TO END (`end_to_end` of the bench line): 16 cfg2 clips x 400 steps through `ClipFitter`, 8 per batch, wall clock from the per-frame input dicts on the host to the results on the host - the first batch builds model / workspaces / graph, the second is copied into the resident stepper | **@E2E@ clips/s** over all 16; a clip of a RESIDENT shape: **@E2ERES@ clips/s**, input load = @E2ESETUP@ of its fit; split: @E2ESPLIT@ |
 | cfg5 on one rank (8 clips, step-2, one tied scale, RCCL call issued) | @CFG5@ it/s |
 | 2 ranks on ONE GPU through gloo (the driver's `torch.distributed.run` line; weak scaling has nothing to scale on one GPU - this is the N > 1 code path, not a speed-up) | cfg2: @G2@ it/s summed; cfg5 (2 x 4 clips, tied scale): @G5@ it/s, replicas identical |
-| object-pose initialisation (SURVEY §8f rank 1): 500 candidate poses of the bottle against one 256² mask, `python bench.py --pose-init 500` | **@POSE@ pose-steps/s** (@POSEMS@ ms per step of 500 poses; a 50-step fit in @POSEFIT@ s); by loop: @POSELOOPS@; CPU oracle @POSECPU@ pose-steps/s |
+| object-pose initialisation (SURVEY §8f rank 1): 500 candidate poses of the bottle against one 256² mask, `python bench.py --full --pose-init 500` | **@POSE@ pose-steps/s** (@POSEMS@ ms per step of 500 poses; a 50-step fit in @POSEFIT@ s); by loop: @POSELOOPS@; CPU oracle @POSECPU@ pose-steps/s |
 | free-running parity, cfg2 at full size, 400 steps, HIP loop vs the oracle's reproducible loop (`profiles/r06_freerun_cfg2_400.json`) | every parameter (object pose, hand pose, MANO) bit-equal after every step: @FREEALL@ (object alone: @FREEEQ@), final vertices object @FREEVO@ mm / hand @FREEVH@ mm, largest relative loss difference at any step @FREELOSS@ (section 2; the control `r04_control_cfg2_400.json`: the CPU loop against itself from inputs 1e-7 m apart ends 0.85 mm apart) |
 | CPU baseline (oracle loop, 64 host threads) | @CPU@ it/s with the reference's per-step `.item()` logging, @CPUOFF@ it/s without → GPU / CPU ≈ @RATIO@ × (target ≥ 50 ×) |
 | whole iteration vs the SURVEY §8d byte model (144.1 MB) | @WHOLE@ of 8 TB/s at one clip |
@@ -397,7 +398,7 @@ percentile 21.8 µs) = 41 µs.  No phase is more than 30 % of a workgroup; the t
 with box-carrying bin entries requested speculatively; two covered samples per trip of the unit body) measured +2 µs and ±0
 (EXPERIMENTS.md).
 
-Pose initialisation (`bench.py --pose-init 500`, its own line with `roofline`; `profiles/r06_p_poseinit_kernel_stats.txt`,
+Pose initialisation (`bench.py --full --pose-init 500`, its own line with `roofline`; `profiles/r06_p_poseinit_kernel_stats.txt`,
 `r06_pmc_poseinit.json`): per step of 500 candidate poses `k_bwd_sweep` @PISWP@ µs (algorithmic 338 MB → @PISWPG@ GB/s =
 **@PISWPF@** of HBM peak, the dominant kernel), `k_raster_fwd` @PIRAS@ µs (@PIRASF@), `k_bwd_lines` @PILIN@ µs (@PILINF@); all
 throughput-bound at 500 frames per launch (these are the launches of ONE loop over all 500 candidates, alone on the GPU - the shape

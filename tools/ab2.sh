@@ -1,13 +1,13 @@
 #!/bin/bash
 # same-box A/B of two builds of libhoman_amd.so (alternated): headline / steady state / 8-clip batch of the default workload with
 # the in-graph kernel times, then the pose initialisation.   usage: tools/ab2.sh variants/lib_a.so homan_amd/lib/libhoman_amd.so [reps]
-A=$1; B=$2; REPS=${3:-2}
+A=$1; B=$2; REPS=${3:-2}; D=$(mktemp)
 for rep in $(seq $REPS); do
   for L in $A $B; do
-    HOMAN_AMD_LIB=$L HOMAN_BENCH_DETAIL=/tmp/ab2_detail.json python bench.py --no-cpu-baseline --legs '' --multi-clip 8 > /dev/null 2>&1
-    python - "$L" <<'PY'
+    HOMAN_AMD_LIB=$L HOMAN_BENCH_DETAIL=$D python bench.py --full --no-cpu-baseline --legs '' --multi-clip 8 > /dev/null 2>&1
+    python - "$L" "$D" <<'PY'
 import json, sys
-d = json.load(open("/tmp/ab2_detail.json"))
+d = json.load(open(sys.argv[2]))
 k = (d.get("steady_state") or {}).get("roofline", {}).get("kernels", {})
 print(sys.argv[1], "it/s %.0f" % d["value"], "steady %.0f" % (d.get("steady_state") or {}).get("value", 0),
       "batch8 %.0f" % (d.get("multi_clip") or {}).get("value", 0),

@@ -11,7 +11,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_LDS_ATOMIC SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVES"; do
   i=$((i+1))
-  HOMAN_POSEINIT_LOOPS=fused rocprofv3 --kernel-trace --pmc $set -d $O -o p$i -- python $R/bench.py --pose-init $N --steps 30 --no-cpu-baseline > $O/run$i.log 2>&1
+  HOMAN_POSEINIT_LOOPS=fused rocprofv3 --kernel-trace --pmc $set -d $O -o p$i -- python $R/bench.py --full --pose-init $N --steps 30 --no-cpu-baseline > $O/run$i.log 2>&1
 done
 cd $R
 python - "$O" "$LAST" "$N" <<'PY'

@@ -43,7 +43,7 @@ fi
 # bench lines: the COMPACT line bench.py prints goes to *_line.json, the full record (bench.py's detail file) to *.json
 b() { # name, bench flags...
   n=$1; shift
-  HOMAN_BENCH_DETAIL=$O/${N}_bench_$n.json python bench.py "$@" > $O/${N}_bench_${n}_line.json 2> $O/${N}_bench_$n.err
+  HOMAN_BENCH_DETAIL=$O/${N}_bench_$n.json python bench.py --full "$@" > $O/${N}_bench_${n}_line.json 2> $O/${N}_bench_$n.err
 }
 b cfg2_driver_flags --gpus 1 --steps 20 --warmup 5          # the driver's command: iterations 5-25 of a fresh fit
 b cfg2 --parity                                             # the default workload + the opt-in parity / end-to-end legs
@@ -59,14 +59,14 @@ python tools/bench_clips.py --clips 8 --steps 200 --mixed > $O/${N}_bench_mixed_
 HOMAN_BENCH_BACKEND=gloo b cfg2_gpus2_gloo --gpus 2 --steps 200 --warmup 20 --multi-clip 2 --steady 0
 HOMAN_BENCH_BACKEND=gloo b cfg5_gpus2_gloo --gpus 2 --shared-scale --multi-clip 4 --steps 100 --warmup 10
 cd /tmp && export TMPDIR=/tmp
-HEAD="python bench.py --multi-clip 0 --no-cpu-baseline --legs ''"
-HOMAN_BENCH_DETAIL=$O/${N}_bench_cfg2_profiled.json rocprofv3 --kernel-trace --stats -d $O/ph -o ph -- python $R/bench.py --multi-clip 0 --no-cpu-baseline --legs '' > /dev/null 2>&1
+HEAD="python bench.py --full --multi-clip 0 --no-cpu-baseline --legs ''"
+HOMAN_BENCH_DETAIL=$O/${N}_bench_cfg2_profiled.json rocprofv3 --kernel-trace --stats -d $O/ph -o ph -- python $R/bench.py --full --multi-clip 0 --no-cpu-baseline --legs '' > /dev/null 2>&1
 BATCH="python tools/bench_clips.py --clips 8 --steps 100"
 rocprofv3 --kernel-trace --stats -d $O/pb -o pb -- python $R/tools/bench_clips.py --clips 8 --steps 100 > $O/${N}_bench_batch8_profiled.json 2>/dev/null
-POSE="HOMAN_POSEINIT_LOOPS=fused python bench.py --pose-init 500 --no-cpu-baseline"
-HOMAN_POSEINIT_LOOPS=fused rocprofv3 --kernel-trace --stats -d $O/pp -o pp -- python $R/bench.py --pose-init 500 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $O/pd -o pd -- python $R/bench.py --depth --multi-clip 0 --no-cpu-baseline --steady 0 --legs '' > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $O/p3 -o p3 -- python $R/bench.py --step2 --multi-clip 0 --no-cpu-baseline --steady 0 --legs '' > /dev/null 2>&1
+POSE="HOMAN_POSEINIT_LOOPS=fused python bench.py --full --pose-init 500 --no-cpu-baseline"
+HOMAN_POSEINIT_LOOPS=fused rocprofv3 --kernel-trace --stats -d $O/pp -o pp -- python $R/bench.py --full --pose-init 500 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $O/pd -o pd -- python $R/bench.py --full --depth --multi-clip 0 --no-cpu-baseline --steady 0 --legs '' > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $O/p3 -o p3 -- python $R/bench.py --full --step2 --multi-clip 0 --no-cpu-baseline --steady 0 --legs '' > /dev/null 2>&1
 cd $R
 python tools/prof_summary.py $O/pd/pd_results.db "python bench.py --depth --multi-clip 0 --no-cpu-baseline --steady 0" > $O/${N}_p_cfg2_depth_kernel_stats.txt
 python tools/prof_timeline.py $O/pd/pd_results.db > $O/${N}_p_cfg2_depth_timeline.txt
