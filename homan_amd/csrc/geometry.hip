@@ -421,7 +421,6 @@ __global__ void k_sum_small(const float* __restrict__ parts, int n, float w0, co
     if (threadIdx.x == 0) out[c] = w0 * a + (extra ? w1 * extra[c] : 0.f);
 }
 
-thread_local int g_hm_lds_pad[HM_PAD_FAMILIES] = {0, 0, 0, 0, 0, 0, 0, 0};
 extern "C" {
 int hm_lincomb4(const float* a0, float w0, const float* a1, float w1, const float* a2, float w2, const float* a3,
                 float w3, long n, float* out, hipStream_t stream)
@@ -454,26 +453,7 @@ int hm_rigid_fwd(const float* mesh, const float* rot6d, const float* trans, cons
 {
     return hm_rigid_fwd_clips(mesh, rot6d, trans, scale, abs_scale, N, V, rotmat, verts, 0, stream);
 }
-// see hm_common.h: family 0 MANO forward, 1 MANO backward, 2 smoothness / interaction / hand-terms launches, 3 the fused
-// pair-terms launch, 4 rigid backward.  Per calling thread (thread-local), read at launch (or capture).  Returns the previous value; bytes < 0 queries.
-int hm_tune_lds_pad(int family, int bytes)
-{
-    if (family < 0 || family >= HM_PAD_FAMILIES) return -1;
-    const int prev = g_hm_lds_pad[family];
-    if (bytes >= 0) g_hm_lds_pad[family] = bytes;
-    return prev;
-}
 #define RIGID_MAX_CHUNKS 16
-// Scheduling hint, no effect on results (the sums are exact): 1 = the object's rigid backward of the fused loops as ceil(V / 256)
-// small workgroups per frame + ticket instead of one large workgroup per frame.  Per calling thread (thread-local), read at launch (or capture).
-// Returns the previous value; < 0 only queries.
-static thread_local int g_rigid_chunked = 1;      // (same-box A/B, cfg2: chunked 6295 it/s, one 768-thread workgroup per frame 6110)
-int hm_tune_rigid_chunked(int enable)
-{
-    const int prev = g_rigid_chunked;
-    if (enable >= 0) g_rigid_chunked = enable ? 1 : 0;
-    return prev;
-}
 size_t hm_rigid_workspace_bytes(int N) { return (((size_t)N * 4 + 255) & ~(size_t)255) + (size_t)N * RIGID_MAX_CHUNKS * 32 * 4; }
 static int rigid_bwd_launch(const float* mesh, const float* rot6d, const float* scale, int abs_scale,
                             const float* const* g_terms, const float* weights, int n_terms, SilGather sil,
@@ -495,31 +475,32 @@ static int rigid_bwd_launch(const float* mesh, const float* rot6d, const float* 
     const int chunks = workspace ? min(RIGID_MAX_CHUNKS, hm_cdiv(V, exact ? threads : 4 * threads)) : 1;
     unsigned int* cnt = (unsigned int*)workspace;
     float* partials = workspace ? (float*)((char*)workspace + (((size_t)N * 4 + 255) & ~(size_t)255)) : nullptr;
-    // one workgroup per frame whenever the mesh fits: <= 1024 vertices one per thread, <= 1536 two per thread on 768 threads (12
-    // waves: 170 registers each, the 64 of the staged double2 loads included - at 1024 threads the 128-register cap spilled)
-    // (meshes beyond 16 chunks of 256 vertices: 768 threads x 2 vertices per chunk, up to 24 576 vertices)
-    const bool small = g_rigid_chunked && V <= RIGID_MAX_CHUNKS * 256;
-    const int nv = small ? 1 : (V > 1024 ? 2 : 1);
-    const int thr = small ? 256 : (nv == 2 ? 768 : (V > 512 ? 1024 : (V > 256 ? 512 : 256)));
+    // meshes of up to 16 chunks of 256 vertices: ceil(V / 256) workgroups of 256 threads per frame, one vertex per thread
+    // (same-box A/B, cfg2: 6295 it/s against 6110 with one 768-thread workgroup per frame; the sums are exact, results do not
+    // depend on the split).  Larger meshes: 768 threads x 2 vertices per chunk, up to 24 576 vertices (12 waves: 170 registers
+    // each, the 64 of the staged double2 loads included - at 1024 threads the 128-register cap spilled)
+    const bool small = V <= RIGID_MAX_CHUNKS * 256;
+    const int nv = small ? 1 : 2;
+    const int thr = small ? 256 : 768;
     if (exact && !g_rigid && !g_frame && !g_mesh && (workspace ? V <= RIGID_MAX_CHUNKS * thr * nv : V <= thr * nv)) {
         // (the fused loops' object chain: stage-wise loads of NV vertices per thread, see k_rigid_bwd_x)
         const int ch = hm_cdiv(V, thr * nv);
         const double magic = hm_sum_magic(sum_log2q);
         if (nv == 2)
-            hipLaunchKernelGGL((k_rigid_bwd_x<2, 768>), dim3(N, ch), dim3(thr), g_hm_lds_pad[HM_PAD_RIGID_BWD], stream, mesh, rot6d, scale,
+            hipLaunchKernelGGL((k_rigid_bwd_x<2, 768>), dim3(N, ch), dim3(thr), 0, stream, mesh, rot6d, scale,
                                abs_scale, t, sil, smooth, N, V, g_rot6d, g_trans, g_scale_part, partials, cnt, clip_len ? clip_len : N, magic);
         else
-            hipLaunchKernelGGL((k_rigid_bwd_x<1, 1024>), dim3(N, ch), dim3(thr), g_hm_lds_pad[HM_PAD_RIGID_BWD], stream, mesh, rot6d, scale,
+            hipLaunchKernelGGL((k_rigid_bwd_x<1, 1024>), dim3(N, ch), dim3(thr), 0, stream, mesh, rot6d, scale,
                                abs_scale, t, sil, smooth, N, V, g_rot6d, g_trans, g_scale_part, partials, cnt, clip_len ? clip_len : N, magic);
         return hm_launch_status();
     }
     HM_CHECK_ARG(!smooth.verts);
     if (exact)
-        hipLaunchKernelGGL(k_rigid_bwd<true>, dim3(N, chunks), dim3(threads), g_hm_lds_pad[HM_PAD_RIGID_BWD], stream, mesh, rot6d, scale,
+        hipLaunchKernelGGL(k_rigid_bwd<true>, dim3(N, chunks), dim3(threads), 0, stream, mesh, rot6d, scale,
                            abs_scale, t, sil, g_rigid, g_frame, frame_stride, frame_scale, N, V, g_mesh, g_rot6d, g_trans,
                            g_scale_part, partials, cnt, clip_len ? clip_len : N, hm_sum_magic(sum_log2q));
     else
-        hipLaunchKernelGGL(k_rigid_bwd<false>, dim3(N, chunks), dim3(threads), g_hm_lds_pad[HM_PAD_RIGID_BWD], stream, mesh, rot6d, scale,
+        hipLaunchKernelGGL(k_rigid_bwd<false>, dim3(N, chunks), dim3(threads), 0, stream, mesh, rot6d, scale,
                            abs_scale, t, sil, g_rigid, g_frame, frame_stride, frame_scale, N, V, g_mesh, g_rot6d, g_trans,
                            g_scale_part, partials, cnt, clip_len ? clip_len : N, 0.0);
     return hm_launch_status();

@@ -1,8 +1,6 @@
 """FusedStepper: the whole optimisation iteration (reference homan/jointopt.py:158-192 over homan/homan.py:421-508) as a fixed
 sequence of C-ABI kernel launches on two or three HIP streams, captured in hipGraphs - the benchmark path.  One clip, a batch
 of equal-shaped clips (homan_amd.clipbatch), or - through homan_amd.shard - a shard of clips of any shapes."""
-import ctypes
-import os
 from collections import OrderedDict, defaultdict
 
 import numpy as np
@@ -74,6 +72,12 @@ class FusedStepper:
     SLOTS = ["loss_pca", "loss_scale_obj", "loss_scale_hand", "loss_smooth_obj", "loss_smooth_hand", "loss_collision",
              "loss_contact", "loss_v2d_hand", "v2d_hand", "loss_sil_obj", "iou_object", "loss_inter",
              "handobj_maxdist", "loss_depth"]
+    # the raster's launch order follows the measured cost of its workgroups from iteration to iteration (hm_tune_raster_reorder,
+    # captured with the iteration; same-box A/B: raster 57 -> 45 us inside the graph at one clip, 356 -> 298 us at eight; the
+    # iteration: clip batches and the step-2 sets +0.3..1 %, one-clip step-1 fits +4 % in the steady state and over iterations
+    # 5-25 - but only since the metric-only search got shorter: while the hand-side chain was as long as the silhouette chain
+    # it had been running in the raster's tail and a shorter raster pushed it under the sweeps, -4 %)
+    raster_reorder = 1
 
     def __init__(self, model, loss_weights, lr, max_steps, capture=True, shared_scale=False, group=None, collectives=True):
         from . import constants, ops
@@ -115,33 +119,25 @@ class FusedStepper:
         self.B, self.C, self.clip_len, self.NS = B, C, m.clip_len, NS
         # third stream for the silhouette reduction + log row: it pays on a clip batch (+1.5 %); at one clip the graph executor
         # spends two cross-queue hops (~10 us each) on it, and two streams are 5-6 % faster (same-box A/B, cfg2 and cfg3)
-        self.use_aux = (os.environ.get("HOMAN_AUX") or ("1" if C > 1 else "0")) != "0"
-        if lw.get("lw_depth", 0) > 0:
-            self.use_aux = False         # (with the depth launches on the side stream the three-stream graph dies at replay in
-                                         #  the HIP runtime, like the other patterns listed at _loop_streams: two streams)
+        # (with the depth launches on the side stream the three-stream graph dies at replay in the HIP runtime, like the other
+        #  patterns listed at _loop_streams: two streams)
+        self.use_aux = C > 1 and not lw.get("lw_depth", 0) > 0
         # two streams, no shared scale: the log row of a step is written by the Adam launch itself (one launch less)
-        self.log_in_adam = (not self.use_aux and not self.shared_scale and
-                            os.environ.get("HOMAN_LOG_IN_ADAM", "1") != "0")
-        self.fork_after_setup = os.environ.get("HOMAN_FORK_AFTER_SETUP", "1") != "0"
-        # the depth renders write into buffers this stepper owns and keeps passing: a region that is empty again leaves the empty
-        # pattern it wrote last time alone (hm_sil_fwd's persistent_outputs, as the silhouette render does) - at the full-image
-        # camera nine regions in ten are background
-        self.depth_persistent = int(os.environ.get("HOMAN_DEPTH_PERSISTENT", "1") != "0")
+        self.log_in_adam = not self.use_aux and not self.shared_scale
         # the side stream forms the camera-space object vertices ITSELF (hm_rigid_fwd_clips into a buffer of its own: the face
         # setup's arithmetic, the same floats) instead of waiting for the face setup's copy: the silhouette chain then has no
         # successor on another queue between the iteration's fork and its join - the rasteriser follows the face setup without
         # the few microseconds a node with a cross-queue successor costs its own queue (EXPERIMENTS r6)
         # (not on the step-2 sets: there the hand-side chain is the longer one, and one more launch on it costs what the
         #  silhouette chain gains - cfg3 5 457 -> 5 221 it/s with it)
-        self.side_own_vo = ((os.environ.get("HOMAN_SIDE_OWN_VO") or "1") != "0" and self.h == 1 and C == 1 and
-                            not lw.get("lw_depth", 0) > 0 and not lw.get("lw_collision", 0) > 0 and not lw.get("lw_contact", 0) > 0)
+        self.side_own_vo = (self.h == 1 and C == 1 and not lw.get("lw_depth", 0) > 0 and not lw.get("lw_collision", 0) > 0 and
+                            not lw.get("lw_contact", 0) > 0)
         # with the ordinal depth term the object's two renders of an iteration - ROI silhouette, full-image depth - are ONE launch
         # pair (hm_sil_fwd_multi; see _issue_silhouette_chain)
-        self.merge_renders = (os.environ.get("HOMAN_MERGE_RENDERS", "1") != "0" and self.h == 1 and lw.get("lw_depth", 0) > 0 and
-                              lw.get("lw_sil_obj", 0) > 0)
+        self.merge_renders = self.h == 1 and lw.get("lw_depth", 0) > 0 and lw.get("lw_sil_obj", 0) > 0
         # the silhouette loss / IoU values (log only) come out of the backward's first launch: one launch less on the chain
         # (two streams only: with the third stream the reduction and the log row stay there, behind the raster's event)
-        self.sil_reduce_in_bwd = not self.use_aux and os.environ.get("HOMAN_SIL_REDUCE_IN_BWD", "1") != "0"
+        self.sil_reduce_in_bwd = not self.use_aux
         self.Vo, self.Vh, self.P = Vo, Vh, m.mano_pca_pose.shape[1]
         f = lambda *shape: torch.zeros(*shape, device=dev)
         N = self.N = B * h                                        # hand rows (hands interleaved frame-major, homan.py:62-63)
@@ -171,10 +167,8 @@ class FusedStepper:
         # stream as a block range.  Until round 6 the step-2 sets launched it on the silhouette chain instead, behind the sweeps
         # (round 3: cfg3 +5 % while the hand side was by far the longer chain); since the hand side's launches were fused the
         # silhouette chain is the longer one there too and an 8 us launch on its tail costs what it lasts: cfg3 5 405 -> 5 510
-        # it/s over iterations 20-420, 5 246 -> 5 304 in the steady state (same box, alternated).  HOMAN_SMOOTH_OBJ_MAIN=1: the old
-        # placement (one clip only: -4 % on a clip batch).
-        self.smooth_obj_on_main = (os.environ.get("HOMAN_SMOOTH_OBJ_MAIN", "0") != "0" and
-                                   (self.on["col"] or self.on["con"]) and m.C == 1)
+        # it/s over iterations 20-420, 5 246 -> 5 304 in the steady state (same box, alternated; on a clip batch the old placement
+        # lost 4 %).
         # unit gradients / scratch
         self.U_pca, self.U_so, self.U_sh = f(N, self.P), f(C), f(C)
         self.U_smo, self.U_smh, self.U_v2d = f(B, Vo, 3), f(N, Vh, 3), f(N, Vh, 3)
@@ -201,8 +195,7 @@ class FusedStepper:
         self.nn_idx = torch.zeros(B, Vh, dtype=torch.int32, device=dev)
         # the metric-only search's seed pairs (per frame the vertex pair that held the minimum at the last iteration: its distance
         # now bounds this iteration's minimum before anything is scanned; hm_nn_fwd_rigid_clips).  Scheduling data only.
-        self.nn_seed = (torch.zeros((2 + (Vh + 127) // 128) * B, dtype=torch.int32, device=dev)
-                        if os.environ.get("HOMAN_NN_SEED", "1") != "0" else None)
+        self.nn_seed = torch.zeros((2 + (Vh + 127) // 128) * B, dtype=torch.int32, device=dev)
         self.nn_d2 = f(B, Vh)
         self.obj_order = _morton_order(m.verts_object_og[0]).to(dev)      # spatial sort of the rigid mesh (metric-only search)
         # ... and of the hand: its template's vertices in the same kind of order, so that the 128 hand vertices of a search
@@ -217,7 +210,6 @@ class FusedStepper:
         with torch.no_grad():
             # (repeats of a real vertex pad the last group: they change nothing but the mean, and are masked out of it)
             self.obj_spheres = self._group_spheres()                                         # (B, ng, 4)
-        self.nn_spheres = os.environ.get("HOMAN_NN_SPHERES", "1") != "0"
         self.pooled = f(B, m.sil_ctx.S, m.sil_ctx.S)
         # silhouettes at a size off the kernels' 32-pixel tile grid (the reference's REND_SIZE is 256): rendered on the next
         # multiple with the first two rows of K rescaled and the masks padded with keep = 0 (ops.SilhouetteContext); all three
@@ -271,8 +263,7 @@ class FusedStepper:
             # non-zero structure of the two gradient images, one byte per (frame, pixel row, 64-pixel segment): the depth-map
             # backward skips faces and frames that touch no flagged segment (the term is zero wherever render and annotation
             # agree on the order); ones = "walk everything" until the first backward has written them
-            self.d_flags = (torch.ones(2, B * Sd * (Sd // 64), dtype=torch.uint8, device=dev)
-                            if Sd % 64 == 0 and os.environ.get("HOMAN_DEPTH_SPARSE", "1") != "0" else None)
+            self.d_flags = torch.ones(2, B * Sd * (Sd // 64), dtype=torch.uint8, device=dev) if Sd % 64 == 0 else None
             self.rws_depth = ClipReduceWorkspace(dev, C)
             self.G_dep_o, self.G_dep_h = f(B, Vo, 3), f(B, Vh, 3)
             self.up_depth = torch.tensor([w["loss_depth"]], device=dev)
@@ -295,41 +286,29 @@ class FusedStepper:
         self.graph = self.graph_b = self.graph_k = None
         # iterations per replay of the second graph (run()): one clip, no collective between the halves of an iteration.  The
         # turnaround between two replays is ~5 us of a 160 us iteration (same-box A/B: +2-3 % at 4, no more at 8 / 16)
-        self.graph_iters = int(os.environ.get("HOMAN_GRAPH_ITERS") or ("4" if C == 1 else "1"))
+        self.graph_iters = 4 if C == 1 else 1
         self.cap_stream, self.side, self.aux, side = _loop_streams(dev)
-        self.ev_vo, self.ev_pair, self.ev_sil, self.ev_fwd, self.ev_smo, self.ev_ras = (torch.cuda.Event() for _ in range(6))
-        self.ev_hand, self.ev_col, self.ev_dep, self.ev_dgrad = (torch.cuda.Event() for _ in range(4))
-        # (option, off: one clip, step-2 sets - the collision chain on the side stream, the rest of the hand side on the third
-        #  stream, see forward_backward; measured +-0.4 % on cfg3: both chains already share a work-bound GPU)
-        self.col_on_aux = (os.environ.get("HOMAN_COL_AUX") or "0") != "0" and C == 1 and self.h == 1
+        self.ev_vo, self.ev_pair, self.ev_sil, self.ev_fwd, self.ev_ras = (torch.cuda.Event() for _ in range(5))
+        self.ev_dep, self.ev_dgrad, self.ev_lines = (torch.cuda.Event() for _ in range(3))
         self.reduce_ws_b = ClipReduceWorkspace(dev, C)
         # (the terms of the fused pair-terms launch run side by side: a reduce workspace each)
         self.reduce_ws_c, self.reduce_ws_d, self.reduce_ws_e = (ClipReduceWorkspace(dev, C) for _ in range(3))
-        # (one clip: the hand-side chain is the iteration's critical path, -6 %; a batch hides that chain under the silhouette
-        #  chain and the fused launch only adds contention there, +1.6 %)
-        # a clip batch: the pair-wise terms wait for the END of the rasteriser.  They used to start there anyway, behind a MANO
-        # forward as long as the raster; since that launch reads the blend matrix once per four frames it is over early, and the
-        # search / smoothness / interaction launches next to the raster cost it more (362 -> 433 us) than they gain next to the
-        # line expansion (230 -> 162 us)
-        self.pairs_after_raster = (self.use_aux and not self.sil_reduce_in_bwd and
-                                   (os.environ.get("HOMAN_PAIRS_AFTER_RASTER") or "1") != "0")
         # a clip batch: the pair-wise terms of the side stream wait for the END of the line expansion (the backward in two
         # calls) - that kernel is latency-bound and takes 200 us instead of 150 next to neighbours that hold its wave slots -
         # and the sweeps run 1024 persistent workgroups instead of 1280 so that the hand's gradient launches find registers
-        # next to them (same-box A/B, 8 clips: step-1 8 650 -> 8 865 it/s, step-2 7 142 -> 7 332; either change alone loses)
-        self.pairs_after_lines = (os.environ.get("HOMAN_PAIRS_AFTER_LINES") or "1") != "0" and C > 1 and self.on["sil"]
-        self.ev_lines = torch.cuda.Event()
+        # next to them (same-box A/B, 8 clips: step-1 8 650 -> 8 865 it/s, step-2 7 142 -> 7 332; either change alone loses).
+        # (Started next to the raster instead, the search / smoothness / interaction launches cost it more - 362 -> 433 us -
+        #  than they gain next to the line expansion - 230 -> 162 us.)
+        self.pairs_after_lines = C > 1 and self.on["sil"]
         # the hand's rigid backward inside the MANO backward's launch (hm_mano_bwd_rigid_clips): one launch less on the hand-side
         # chain.  One clip: cfg2 +1.3 %, cfg3 +1.4 %; a clip batch hides that chain under the silhouette chain and loses 1-1.6 %
         # (round 6: a clip batch too, +0.5 % - the separate hand launch was a 1024-thread workgroup per frame that found no room
         #  next to the persistent sweeps: 106 us on average, up to 365 us in the 8-clip profile of round 5)
         #  (a step-2 batch keeps the separate launch: 7 715 against 7 647 it/s)
-        self.mano_bwd_rigid = (os.environ.get("HOMAN_MANO_BWD_RIGID") or
-                               ("1" if C == 1 or not (self.on["col"] or self.on["con"]) else "0")) != "0"
-        self.nn_early = (os.environ.get("HOMAN_NN_EARLY") or "0") != "0"
-        self.pair_fused = (os.environ.get("HOMAN_PAIR_FUSED") or ("1" if C == 1 else "0")) != "0"
-        self.hand_terms_fused = os.environ.get("HOMAN_HT_FUSED", "1") != "0"
-        self.nn_full_fused = os.environ.get("HOMAN_NN_FULL_FUSED", "1") != "0"
+        self.mano_bwd_rigid = C == 1 or not (self.on["col"] or self.on["con"])
+        # the pair-wise terms in one launch (csrc/pairterms.hip) at one clip: the hand-side chain is the iteration's critical
+        # path, -6 %; a batch hides that chain under the silhouette chain and the fused launch only adds contention there, +1.6 %
+        self.pair_fused = C == 1
         if self.shared_scale:
             self._sync_shared_scale_start()
         side.wait_stream(torch.cuda.current_stream())
@@ -344,44 +323,30 @@ class FusedStepper:
             # up to 32 us late behind background regions of the static order, profiles/r06_raster_trace_depth.txt; with the
             # object's two renders in one launch the hand side is the longer chain: cfg2 + depth 4 151 -> 4 215 it/s, same box);
             # the object's depth render keeps the static order (sorted: +-0 alone, -1 % with the hand's)
-            for tag, ctx in zip("oh", self.dctx[:2]):
-                if tag in os.environ.get("HOMAN_DEPTH_CALIBRATE", "h"):
-                    ctx.calibrate()
+            self.dctx[1].calibrate()
         if capture:
             # scheduling hint baked into the captured launches: with the collision / contact terms the hand-side stream is
             # the longer chain and the persistent edge sweeps should leave it more of the GPU (same results either way;
             # same-box A/B on cfg3, round 2 before the launch fusions: 1280 -> 4030, 768 -> 4130, 512 -> 4194 it/s; after them,
             # with the raster ballast below: 512 -> 4408, 768 -> 4552, 1024 -> 4537, 1280 -> 4512)
-            sb = int(os.environ.get("HOMAN_SWEEP_BLOCKS", "0")) or (768 if (self.on["col"] or self.on["con"]) and C == 1 else
-                                                                    1024 if self.pairs_after_lines else 1280)
-            pad = os.environ.get("HOMAN_RASTER_PAD")
+            sb = 768 if (self.on["col"] or self.on["con"]) and C == 1 else 1024 if self.pairs_after_lines else 1280
             # same idea for the rasteriser: 8 KB of LDS ballast = 4 workgroups per CU instead of 6 leaves registers for the
             # hand-side kernels (cfg3 one clip: 4347 -> 4500 it/s; cfg2, where that chain is short: 5820 -> 5500, so not there)
-            pad = int(pad) if pad is not None else (4096 if (self.on["col"] or self.on["con"]) and C == 1 else 0)
-            # the raster's launch order follows the measured cost of its workgroups from iteration to iteration
-            # (hm_tune_raster_reorder; same-box A/B: raster 57 -> 45 us inside the graph at one clip, 356 -> 298 us at eight; the
-            # iteration: clip batches and the step-2 sets +0.3..1 %, one-clip step-1 fits +4 % in the steady state and over
-            # iterations 5-25 - but only since the metric-only search got shorter: while the hand-side chain was as long as the
-            # silhouette chain it had been running in the raster's tail and a shorter raster pushed it under the sweeps, -4 %)
-            ro = int(os.environ.get("HOMAN_RASTER_REORDER", "1"))
+            pad = 4096 if (self.on["col"] or self.on["con"]) and C == 1 else 0
             # and for the metric-only search of a clip batch: its 1680 small, latency-bound workgroups otherwise take every wave
             # slot of the CUs next to the line expansion (lines 250 -> 226 us, iteration -4.4 % at 3 search workgroups per CU;
             # 2 per CU make the search itself the tail)
-            nn_pad = os.environ.get("HOMAN_NN_PAD")
             # (34 KB: with the sweep's 30.5 KB workgroups a CU then holds 4 sweeps + 1 search, 2 + 2 or 1 + 3 - the mixes the
             #  40 KB ballast gave next to the 28.9 KB workgroups of the float sweeps; at 40 KB the search found room only
             #  next to THREE sweep workgroups and took 297 instead of 137 us, same-box profile)
-            nn_pad = int(nn_pad) if nn_pad is not None else (34816 if C > 1 and not self.on["con"] else 0)
-            fam_pads = [int(x) for x in os.environ.get("HOMAN_FAM_PADS", "0,0,0,0,0").split(",")]
+            nn_pad = 34816 if C > 1 and not self.on["con"] else 0
             # the hints are per-thread values read when a launch is issued (= captured): set, capture, restore - whatever
             # happens in between (a capture that raises must not leave them changed for the next stepper)
             tune = _lib.lib()
             prev = tune.hm_tune_sweep_blocks(sb)
             prev_pad = tune.hm_tune_raster_lds_pad(pad)
-            prev_reorder = tune.hm_tune_raster_reorder(ro)
+            prev_reorder = tune.hm_tune_raster_reorder(self.raster_reorder)
             prev_nn_pad = tune.hm_tune_nn_lds_pad(nn_pad)
-            prev_fam = [tune.hm_tune_lds_pad(i, v) for i, v in enumerate(fam_pads)]
-            prev_rc = tune.hm_tune_rigid_chunked(int(os.environ.get("HOMAN_RIGID_CHUNKED", "1")))
             try:
                 self.graph = _lib.new_graph()
                 with torch.cuda.graph(self.graph, stream=self.cap_stream):
@@ -405,9 +370,6 @@ class FusedStepper:
                 tune.hm_tune_raster_lds_pad(prev_pad)
                 tune.hm_tune_raster_reorder(prev_reorder)
                 tune.hm_tune_nn_lds_pad(prev_nn_pad)
-                for i, v in enumerate(prev_fam):
-                    tune.hm_tune_lds_pad(i, v)
-                tune.hm_tune_rigid_chunked(prev_rc)
 
     # ---- other clips into the resident stepper
     def reload(self, clip_inputs):
@@ -560,7 +522,7 @@ class FusedStepper:
         main = torch.cuda.current_stream()
         return SimpleNamespace(m=m, L=self.L, P=P, ck=_lib.check, B=self.B, Vo=self.Vo, Vh=self.Vh, c=self.c, on=self.on, w=self.w,
                                CL=self.clip_len, NS=self.NS, C=self.C, main=main, side=self.side, sa=main.cuda_stream,
-                               sb=self.side.cuda_stream, rws_a=P(m.reduce_ws.buf), rws_b=P(self.reduce_ws_b.buf), sctx=m.sil_ctx,
+                               sb=self.side.cuda_stream, rws_b=P(self.reduce_ws_b.buf), sctx=m.sil_ctx,
                                cctx=m.collision_ctx, pca=m.mano_pca_pose, rot=m.mano_rot, betas=m.mano_betas,
                                mtr=m.mano_trans if m.optimize_mano else None, npca=self.P * self.clip_len,      # PCA entries of one clip
                                use_aux=self.use_aux, log=log)
@@ -578,9 +540,7 @@ class FusedStepper:
         # behind that chain, +20 us on the iteration.)
         with torch.cuda.stream(self.aux):
             self.aux.wait_event(self.ev_fwd)
-            if on["smooth"] and self.smooth_obj_on_main:
-                self.aux.wait_event(self.ev_smo)         # (that loss value comes from the calling stream here)
-            if on["sil"] and not self.sil_reduce_in_bwd:
+            if on["sil"]:
                 self.aux.wait_event(self.ev_ras)
                 ck(L.hm_sil_reduce_clips(B, Vo, sctx.F, sctx.S, P(m.keep_sum), self._slot("loss_sil_obj"), None,
                                          P(sctx.workspace), CL, NS, self.aux.cuda_stream), "sil_reduce")
@@ -604,48 +564,34 @@ class FusedStepper:
                 # full-image camera) as ONE face-setup launch and ONE raster launch (hm_sil_fwd_multi: per render the arguments
                 # of the two calls below, the depth render forming its vertices from the pose like the silhouette render does -
                 # the same floats as self.vo); each render keeps its workspace, the backward passes are unchanged
+                # the DEPTH render's workgroups first: it lasts as long as its slowest workgroup (37 us: one region with 240
+                # candidates, profiles/r06_raster_trace_depth.txt), which then runs under the silhouette render's two rounds
+                # instead of behind them (cfg2 + depth 4 208 -> 4 303 it/s, same box; results do not depend on the order)
                 arr = _lib.sil_renders([
-                    dict(verts=m.verts_object_og, faces=sctx.faces, K=self.sil_K, B=B, V=Vo, F=sctx.F, S=sctx.S, orig_size=1.0,
-                         znear=self.ops.NMR_NEAR, zfar=self.ops.NMR_FAR, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
-                         work_order=sctx.work_order, rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object,
-                         rigid_scale=m.int_scales_object, rigid_abs=1, persistent_outputs=1, workspace=sctx.workspace, clip_len=CL,
-                         cam_verts_out=self.vo),
                     dict(verts=m.verts_object_og, faces=self.dctx[0].faces, K=m.camintr, B=B, V=Vo, F=self.dctx[0].F,
                          S=self.dctx[0].S, orig_size=1.0, znear=self.ops.NMR_NEAR, zfar=self.ops.NMR_FAR, pooled=self.d_sil_o,
                          pooled_depth=self.d_dep_o, work_order=self.dctx[0].work_order, rigid_rot6d=m.rotations_object,
                          rigid_trans=m.translations_object, rigid_scale=m.int_scales_object, rigid_abs=1,
-                         persistent_outputs=self.depth_persistent, workspace=self.dctx[0].workspace, clip_len=CL)])
-                if os.environ.get("HOMAN_MERGE_ORDER", "1") == "1":
-                    # the DEPTH render's workgroups first: it lasts as long as its slowest workgroup (37 us: one region with 240
-                    # candidates, profiles/r06_raster_trace_depth.txt), which then runs under the silhouette render's two rounds
-                    # instead of behind them (cfg2 + depth 4 208 -> 4 303 it/s, same box; results do not depend on the order)
-                    tmp = _lib.SilRender()
-                    ctypes.memmove(ctypes.byref(tmp), ctypes.byref(arr[0]), ctypes.sizeof(tmp))
-                    ctypes.memmove(ctypes.byref(arr[0]), ctypes.byref(arr[1]), ctypes.sizeof(tmp))
-                    ctypes.memmove(ctypes.byref(arr[1]), ctypes.byref(tmp), ctypes.sizeof(tmp))
-                if self.fork_after_setup:
-                    ck(L.hm_sil_fwd_multi(arr, 2, 1, sa), "sil_fwd_multi(setup)")
-                    self.ev_sil.record(main)
-                    ck(L.hm_sil_fwd_multi(arr, 2, 2, sa), "sil_fwd_multi(raster)")
-                else:
-                    ck(L.hm_sil_fwd_multi(arr, 2, 3, sa), "sil_fwd_multi")
-                    self.ev_sil.record(main)
+                         persistent_outputs=1, workspace=self.dctx[0].workspace, clip_len=CL),
+                    dict(verts=m.verts_object_og, faces=sctx.faces, K=self.sil_K, B=B, V=Vo, F=sctx.F, S=sctx.S, orig_size=1.0,
+                         znear=self.ops.NMR_NEAR, zfar=self.ops.NMR_FAR, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
+                         work_order=sctx.work_order, rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object,
+                         rigid_scale=m.int_scales_object, rigid_abs=1, persistent_outputs=1, workspace=sctx.workspace, clip_len=CL,
+                         cam_verts_out=self.vo)])
+                ck(L.hm_sil_fwd_multi(arr, 2, 1, sa), "sil_fwd_multi(setup)")
+                self.ev_sil.record(main)
+                ck(L.hm_sil_fwd_multi(arr, 2, 2, sa), "sil_fwd_multi(raster)")
                 self.ev_dep.record(main)
             elif self.side_own_vo:
                 ck(L.hm_sil_fwd_clips(*fwd_args, sa), "sil_fwd")      # (no successor on the side stream: see side_own_vo)
-            elif self.fork_after_setup:
+            else:
                 # the face setup (which also writes the camera-space vertices self.vo), the fork of the side stream, then the
                 # rasteriser: the pair-wise losses do not wait for the raster and the raster has one successor on its chain
                 ck(L.hm_sil_fwd_phase_clips(*fwd_args, 1, sa), "sil_fwd(setup)")
                 self.ev_sil.record(main)
                 ck(L.hm_sil_fwd_phase_clips(*fwd_args, 2, sa), "sil_fwd(raster)")
-                if use_aux and not self.sil_reduce_in_bwd:
+                if use_aux:
                     self.ev_ras.record(main)     # the tile partials of the fused loss, for the reduction on the third stream
-            else:
-                ck(L.hm_sil_fwd_clips(*fwd_args, sa), "sil_fwd")      # (also writes the camera-space vertices self.vo)
-                self.ev_sil.record(main)         # self.vo for the side stream
-                if use_aux and not self.sil_reduce_in_bwd:
-                    self.ev_ras.record(main)
             if on["depth"] and not self.merge_renders:
                 # the OBJECT's depth render of the ordinal depth term rides this chain, right behind the silhouette raster (its
                 # vertices are the face setup's): the hand's render runs on the side stream meanwhile - two renders after each
@@ -675,7 +621,6 @@ class FusedStepper:
         if not on["sil"]:    # (with the silhouette term the face setup of hm_sil_fwd has written self.vo already)
             ck(L.hm_rigid_fwd_clips(P(m.verts_object_og), P(m.rotations_object), P(m.translations_object),
                                     P(m.int_scales_object), 1, B, Vo, None, P(self.vo), CL, sb), "rigid_fwd(obj)")
-            self.ev_vo.record(side)
         elif self.side_own_vo:
             ck(L.hm_rigid_fwd_clips(P(m.verts_object_og), P(m.rotations_object), P(m.translations_object),
                                     P(m.int_scales_object), 1, B, Vo, None, P(self.vo_b), CL, sb), "rigid_fwd(obj, side copy)")
@@ -689,15 +634,13 @@ class FusedStepper:
                                     P(m.int_scales_hand), 0, B, Vh, None, P(self.vh), CL, sb), "rigid_fwd(hand)")
         pri = on["pca"] or on["so"] or on["sh"]
         # pair terms that feed nothing to each other go in ONE launch (csrc/pairterms.hip): the interaction term, the
-        # object's smoothness when it rides this stream, the metric-only search (no contact term) and the hand-only
-        # reductions
-        sm_here = on["smooth"] and not self.smooth_obj_on_main
+        # object's smoothness, the metric-only search (no contact term) and the hand-only reductions
         fuse = self.pair_fused and on["inter"] and Vo <= 4096 and not self.inter_min
         nn_fused = fuse and not on["con"]
         # with the contact term the FULL search (nearest object vertex of every hand vertex) is the launch's first block
         # range instead, and the contact launches follow it: one launch less on the hand-side chain of the step-2 sets
-        nn_full_fused = fuse and on["con"] and self.nn_full_fused
-        ht_fused = fuse and self.hand_terms_fused and on["smooth"] and on["v2d"]
+        nn_full_fused = fuse and on["con"]
+        ht_fused = fuse and on["smooth"] and on["v2d"]
         ht_args = (P(m.ref_verts2d_hand), float(m.image_size), P(self.U_v2d), self._slot("loss_v2d_hand"), P(self.U_smh),
                    self._slot("loss_smooth_hand"), P(pca) if pri else None, npca,
                    P(m.int_scales_object), P(m.int_scale_object_mean), P(m.int_scales_hand),
@@ -718,98 +661,74 @@ class FusedStepper:
             if on["v2d"]:
                 ck(L.hm_v2d_fwd_clips(P(self.vh), P(m.camintr), 1, P(m.ref_verts2d_hand), float(m.image_size), B, Vh,
                                       P(self.U_v2d), self._slot("loss_v2d_hand"), rws_b, CL, NS, sb), "v2d")
-        nn_early = False
         if on["sil"]:
             if not self.side_own_vo:
                 side.wait_event(self.ev_sil)     # self.vo: camera-space object vertices from the calling stream
             if self.pairs_after_lines:
-                # (the metric-only search - it feeds nothing but the logged hand-object distance, and is the longest
-                #  launch of the hand side in a batch - can run before that wait, next to the rasteriser)
-                nn_early = self.nn_early and on["inter"] and not on["con"] and Vo <= 4096 and not self.inter_min
-                if nn_early:
-                    ck(L.hm_nn_fwd_rigid_clips(P(self.vh), P(self.vo_b), B, Vh, Vo, None, None, self._slot("handobj_maxdist"),
-                                               rws_b, CL, NS, P(self.obj_order),
-                                               (P(self.obj_spheres) if self.nn_spheres else None), P(m.rotations_object),
-                                               P(m.translations_object), P(m.int_scales_object), P(self.hand_order),
-                                               P(self.nn_seed), sb), "nn")
                 side.wait_event(self.ev_lines)   # (scheduling only, see the silhouette chain above)
-            elif self.pairs_after_raster:
-                side.wait_event(self.ev_ras)     # (scheduling only, see __init__)
-        # one clip, step-2 sets: the collision term (five SDF launches) and the search / contact / interaction launches
-        # both start from the two vertex buffers and feed nothing to each other.  The collision chain stays on this
-        # stream; everything else of the hand side - and, behind both, the hand's gradient launches - moves to the third
         it.fuse = fuse
         it.ht_args = ht_args
         it.ht_fused = ht_fused
-        it.nn_early = nn_early
         it.nn_full_fused = nn_full_fused
         it.nn_fused = nn_fused
-        it.sm_here = sm_here
 
     def _issue_pair_terms(self, it):
-        """B: collision, nearest-vertex search, contact, interaction (centroid or min) - on the side stream, or split over two"""
-        (m, L, P, ck, B, Vo, Vh, c, on, w, CL, NS, side, sb, rws_b, cctx, use_aux, fuse, ht_args, ht_fused, nn_early, nn_full_fused, nn_fused, sm_here) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.c, it.on, it.w, it.CL, it.NS, it.side, it.sb, it.rws_b, it.cctx, it.use_aux, it.fuse, it.ht_args, it.ht_fused, it.nn_early, it.nn_full_fused, it.nn_fused, it.sm_here)
-        # stream, which joins the calling stream (the HIP graph runtime crashes at replay when a forked stream rejoins
-        # the SIDE stream: measured twice; forks that rejoin the origin are fine)
-        split = on["col"] and self.col_on_aux and not use_aux
-        side2, sb2 = (self.aux, self.aux.cuda_stream) if split else (side, sb)
+        """B: collision, nearest-vertex search, contact, interaction (centroid or min) - on the side stream"""
+        (m, L, P, ck, B, Vo, Vh, c, on, w, CL, NS, side, sb, rws_b, cctx, fuse, ht_args, ht_fused, nn_full_fused, nn_fused) = \
+            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.c, it.on, it.w, it.CL, it.NS, it.side, it.sb, it.rws_b, it.cctx, it.fuse, it.ht_args, it.ht_fused, it.nn_full_fused, it.nn_fused)
         if on["col"]:
-            if split:
-                self.ev_hand.record(side)        # both vertex buffers exist on this stream from here on
+            # (one clip, step-2 sets: the collision chain alone here and the rest of the hand side on the third stream, which
+            #  then joins the calling stream - the HIP graph runtime crashes at replay when a forked stream rejoins the SIDE
+            #  stream - measured +-0.4 % on cfg3: both chains already share a work-bound GPU)
             ck(L.hm_collision_fwd_clips(P(self.vh), P(cctx.f0), Vh, cctx.f0.shape[0], P(self.vo_b), P(cctx.f1), Vo,
                                         cctx.f1.shape[0], B, c.SDF_SCALE_FACTOR, P(self.U_colh), P(self.U_colo),
                                         self._slot("loss_collision"), P(cctx.ws), CL, NS, sb), "collision")
-            if split:
-                self.ev_col.record(side)
-                side2.wait_event(self.ev_hand)
-        if sm_here and not fuse:
+        if on["smooth"] and not fuse:
             ck(L.hm_smooth_fwd_clips(P(self.vo_b), B, Vo, 1, P(self.U_smo), self._slot("loss_smooth_obj"), rws_b, CL, NS,
-                                     sb2), "smooth(obj)")
-        def search_and_contact(stream_obj, rws):
-            sx = stream_obj.cuda_stream
-            if (on["con"] or on["inter"]) and not nn_fused and not nn_full_fused and not nn_early:
+                                     sb), "smooth(obj)")
+        def search_and_contact():
+            if (on["con"] or on["inter"]) and not nn_fused and not nn_full_fused:
                 # (without the contact term only the logged distance is needed: metric-only search - its group table
                 #  covers 4096 object vertices, larger meshes take the full search for the same number)
                 full = on["con"] or Vo > 4096 or self.inter_min      # ('min' names the closest PAIR: indices needed)
                 ck(L.hm_nn_fwd_rigid_clips(P(self.vh), P(self.vo_b), B, Vh, Vo, P(self.nn_idx) if full else None,
-                                           P(self.nn_d2) if full else None, self._slot("handobj_maxdist"), rws, CL, NS,
-                                           P(self.obj_order), (P(self.obj_spheres) if self.nn_spheres else None), P(m.rotations_object),
+                                           P(self.nn_d2) if full else None, self._slot("handobj_maxdist"), rws_b, CL, NS,
+                                           P(self.obj_order), P(self.obj_spheres), P(m.rotations_object),
                                            P(m.translations_object), P(m.int_scales_object), P(self.hand_order),
-                                           None if full else P(self.nn_seed), sx), "nn")
+                                           None if full else P(self.nn_seed), sb), "nn")
             if on["con"]:
                 ck(L.hm_contact_fwd_clips(P(self.vh), P(self.vo_b), P(self.nn_idx), B, Vh, Vo, c.COLLISION_THRESH,
-                                          P(self.U_conh), P(self.U_cono), self._slot("loss_contact"), rws, CL, NS, sx),
+                                          P(self.U_conh), P(self.U_cono), self._slot("loss_contact"), rws_b, CL, NS, sb),
                    "contact")
         # (the search on a third stream at one clip / step 1: +1 %; -9 % on an 8-clip batch.  Search + contact as a third
         #  branch next to the collision term: the HIP graph runtime crashes at replay when two side branches wait for
         #  each other's events.  Capturing the hand-side forward kernels BEFORE the silhouette chain: -38 %.)
         if not nn_full_fused:
-            search_and_contact(side2, rws_b)
+            search_and_contact()
         if fuse:
             ck(L.hm_pair_terms_fwd_clips(P(self.vh), P(self.vo_b), P(m.camintr), B, Vh, Vo,
                                          self._slot("handobj_maxdist") if (nn_fused or nn_full_fused) else None,
                                          P(self.obj_order), rws_b,
                                          c.INTERACTION_BBOX_EXPANSION, float(c.INTERACTION_Z_THRESH), P(self.rec),
                                          self._slot("loss_inter"), P(self.reduce_ws_c.buf),
-                                         P(self.U_smo) if sm_here else None,
-                                         self._slot("loss_smooth_obj") if sm_here else None, P(self.reduce_ws_d.buf),
+                                         P(self.U_smo) if on["smooth"] else None,
+                                         self._slot("loss_smooth_obj") if on["smooth"] else None, P(self.reduce_ws_d.buf),
                                          *(ht_args if ht_fused else (None, 0.0, None, None, None, None, None, 0, None, None,
                                                                      None, None, None, None, None, None)),
-                                         P(self.reduce_ws_e.buf), (P(self.obj_spheres) if self.nn_spheres else None), P(m.rotations_object),
+                                         P(self.reduce_ws_e.buf), P(self.obj_spheres), P(m.rotations_object),
                                          P(m.translations_object), P(m.int_scales_object), P(self.hand_order),
                                          P(self.nn_idx) if nn_full_fused else None, P(self.nn_d2) if nn_full_fused else None,
-                                         P(self.nn_seed), CL, NS, sb2),
+                                         P(self.nn_seed), CL, NS, sb),
                "pair terms")
             if nn_full_fused:
-                search_and_contact(side2, rws_b)          # (the contact launches only: the search ran above)
+                search_and_contact()          # (the contact launches only: the search ran above)
         elif on["inter"]:
             ck(L.hm_inter_fwd_clips(P(self.vh), P(self.vo_b), P(m.camintr), B, Vh, Vo, c.INTERACTION_BBOX_EXPANSION,
                                     float(c.INTERACTION_Z_THRESH), P(self.rec),
                                     P(self.tmp_inter) if self.inter_min else self._slot("loss_inter"), rws_b, CL,
-                                    NS, sb2), "inter")
+                                    NS, sb), "inter")
         if on["inter"] and self.inter_min:
-            with torch.cuda.stream(side2):
+            with torch.cuda.stream(side):
                 # inter_type "min" (losses.py:219-221): on the frames the gate lets through (rec[:, 0], same gate as the
                 # centroid form) the smallest squared vertex distance; the search names the pair, the term and its
                 # gradient live on the two vertices (hand: rigid pose only - the mesh-detached twin; object: only with a free
@@ -826,23 +745,20 @@ class FusedStepper:
                     self.G_int_o.zero_()
                     self.G_int_o[self.rows, j_star] = -pull
         elif on["inter"] and m.optimize_object_scale:      # the object side of the term reaches the (free) scale: per-vertex form
-            ck(L.hm_inter_bwd(P(self.rec), P(self.up_inter), B, Vh, Vo, None, P(self.G_int_o), sb2), "inter_bwd")
-        it.sb2 = sb2
-        it.side2 = side2
-        it.split = split
+            ck(L.hm_inter_bwd(P(self.rec), P(self.up_inter), B, Vh, Vo, None, P(self.G_int_o), sb), "inter_bwd")
 
     def _issue_depth_terms(self, it):
         """B: ordinal depth term - hand render, pair term per clip, the two depth-map backward passes"""
-        (m, L, P, ck, B, Vo, Vh, on, CL, NS, C, sb2, side2) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.on, it.CL, it.NS, it.C, it.sb2, it.side2)
+        (m, L, P, ck, B, Vo, Vh, on, CL, NS, C, side, sb) = \
+            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.on, it.CL, it.NS, it.C, it.side, it.sb)
         if on["depth"]:
             ctx_o, ctx_h, m_o, m_h = self.dctx
             Sd, K = ctx_o.S, P(m.camintr)
-            self._depth_render(self.vh, ctx_h, Vh, self.d_sil_h, self.d_dep_h, sb2)
+            self._depth_render(self.vh, ctx_h, Vh, self.d_sil_h, self.d_dep_h, sb)
             if on["sil"]:
-                side2.wait_event(self.ev_dep)        # the object's depth image, from the calling stream
+                side.wait_event(self.ev_dep)        # the object's depth image, from the calling stream
             else:
-                self._depth_render(self.vo, ctx_o, Vo, self.d_sil_o, self.d_dep_o, sb2)
+                self._depth_render(self.vo, ctx_o, Vo, self.d_sil_o, self.d_dep_o, sb)
             rw_bytes = L.hm_reduce_workspace_bytes()
             for ci in range(C):           # per clip: the term normalises over the clip's own pairs and mask counts
                 fr = slice(ci * CL, (ci + 1) * CL)
@@ -850,35 +766,32 @@ class FusedStepper:
                         P(m_h[fr]), CL, Sd)
                 ck(L.hm_ordinal_depth_fwd(*args, P(self.d_part[8 * ci * CL:]), P(self.d_rec[ci]),
                                           self._slot("loss_depth") + 4 * NS * ci,
-                                          self.rws_depth.buf.data_ptr() + rw_bytes * ci, sb2), "ordinal depth")
+                                          self.rws_depth.buf.data_ptr() + rw_bytes * ci, sb), "ordinal depth")
                 if self.d_flags is not None:
                     fo = ci * CL * Sd * (Sd // 64)
                     ck(L.hm_ordinal_depth_bwd_flags(*args, P(self.d_rec[ci]), P(self.up_depth), P(self.d_go[fr]), P(self.d_gh[fr]),
-                                                    self.d_flags[0].data_ptr() + fo, self.d_flags[1].data_ptr() + fo, sb2),
+                                                    self.d_flags[0].data_ptr() + fo, self.d_flags[1].data_ptr() + fo, sb),
                        "ordinal depth bwd")
                 else:
                     ck(L.hm_ordinal_depth_bwd(*args, P(self.d_rec[ci]), P(self.up_depth), P(self.d_go[fr]), P(self.d_gh[fr]),
-                                              sb2), "ordinal depth bwd")
+                                              sb), "ordinal depth bwd")
             # the two depth images' backward passes are independent: the hand's stays here, the object's goes to the
             # calling stream (idle between its sweeps and the object's gradient launch) when that stream made the render
-            self.ev_dgrad.record(side2)
+            self.ev_dgrad.record(side)
             for verts, ctx, V_, g, G, li in (((self.vh, ctx_h, Vh, self.d_gh, self.G_dep_h, 1),) if on["sil"] else
                                              ((self.vo, ctx_o, Vo, self.d_go, self.G_dep_o, 0),
                                               (self.vh, ctx_h, Vh, self.d_gh, self.G_dep_h, 1))):
                 ck(L.hm_depth_bwd_sparse(P(verts), K, B, V_, ctx.F, Sd, 1.0, P(g), P(ctx.adj_off), P(ctx.adj_items), P(G),
-                                         P(self.d_flags[li]) if self.d_flags is not None else None, P(ctx.workspace), sb2),
+                                         P(self.d_flags[li]) if self.d_flags is not None else None, P(ctx.workspace), sb),
                    "depth bwd")
 
     def _issue_hand_backward(self, it):
-        """B: join of the split, forward-done / pair-done events, the hand's rigid + MANO backward"""
-        (m, L, P, ck, B, Vh, on, w, CL, pca, rot, betas, mtr, sb2, side2, split) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vh, it.on, it.w, it.CL, it.pca, it.rot, it.betas, it.mtr, it.sb2, it.side2, it.split)
-        if split:
-            side2.wait_event(self.ev_col)    # the collision term's hand gradients, from the side stream
-        self.ev_fwd.record(side2)         # every forward loss value of this stream exists now
-        if not self.smooth_obj_on_main:
-            self._aux_block(it)
-        self.ev_pair.record(side2)        # object-side terms of the pair-wise losses are ready
+        """B: forward-done / pair-done events, the hand's rigid + MANO backward"""
+        (m, L, P, ck, B, Vh, on, w, CL, pca, rot, betas, mtr, side, sb) = \
+            (it.m, it.L, it.P, it.ck, it.B, it.Vh, it.on, it.w, it.CL, it.pca, it.rot, it.betas, it.mtr, it.side, it.sb)
+        self.ev_fwd.record(side)          # every forward loss value of this stream exists now
+        self._aux_block(it)
+        self.ev_pair.record(side)        # object-side terms of the pair-wise losses are ready
         # hand (full path: MANO + rigid): smooth + v2d + collision + contact, summed with their weights inside the rigid
         # backward; the interaction term reaches the rigid pose only, as one vector per frame (rec[:, 2:5] / Vh)
         tp, tw, tn = _lib.terms([(self.U_smh if on["smooth"] else None, w["loss_smooth_hand"]),
@@ -895,34 +808,24 @@ class FusedStepper:
                                          P(betas.grad), P(mtr.grad), P(self.mano_state), P(self.mctx.workspace(B)),
                                          P(self.vm), P(m.rotations_hand), P(m.int_scales_hand), tp, tw, tn, g_rig, g_frm, 8,
                                          w["loss_inter"] / Vh, P(m.rotations_hand.grad), P(m.translations_hand.grad), CL,
-                                         sb2), "mano_bwd + rigid_bwd(hand)")
+                                         sb), "mano_bwd + rigid_bwd(hand)")
         else:
             ck(L.hm_rigid_bwd_clips(P(self.vm if m.optimize_mano else m.verts_hand_og), P(m.rotations_hand),
                                     P(m.int_scales_hand), 0, tp, tw, tn, g_rig, g_frm, 8, w["loss_inter"] / Vh, B, Vh,
                                     P(self.G_mesh) if m.optimize_mano else None, P(m.rotations_hand.grad),
-                                    P(m.translations_hand.grad), None, P(self.rigid_ws_h), CL, sb2), "rigid_bwd(hand)")
+                                    P(m.translations_hand.grad), None, P(self.rigid_ws_h), CL, sb), "rigid_bwd(hand)")
             if m.optimize_mano:
                 ck(L.hm_mano_bwd(self.mctx.ptrs, P(pca), self.P, P(rot), P(betas), B, P(self.G_mesh),
                                  P(self.U_pca) if on["pca"] else None, w["loss_pca"], P(pca.grad), P(rot.grad),
-                                 P(betas.grad), P(mtr.grad), P(self.mano_state), P(self.mctx.workspace(B)), sb2),
+                                 P(betas.grad), P(mtr.grad), P(self.mano_state), P(self.mctx.workspace(B)), sb),
                    "mano_bwd")
 
     def _issue_object_backward(self, it):
-        """A, second half: [object smoothness], [object depth backward], the object's rigid backward with the silhouette gather"""
-        (m, L, P, ck, B, Vo, on, w, CL, NS, main, sa, rws_a, sctx) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.w, it.CL, it.NS, it.main, it.sa, it.rws_a, it.sctx)
+        """A, second half: [object depth backward], the object's rigid backward with the silhouette gather"""
+        (m, L, P, ck, B, Vo, on, w, CL, main, sa, sctx) = \
+            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.w, it.CL, it.main, it.sa, it.sctx)
         # ---------------- A: object backward: silhouette gradient + smooth + contact [+ interaction with a free scale],
         # summed with their weights inside the rigid backward
-        if on["smooth"] and self.smooth_obj_on_main:
-            # the object's smoothness term only feeds the object's pose gradients: it rides the silhouette chain (behind the
-            # sweeps) instead of lengthening the hand-side chain, which is the longer one at one clip
-            if not on["sil"]:
-                main.wait_event(self.ev_vo)
-            ck(L.hm_smooth_fwd_clips(P(self.vo), B, Vo, 1, P(self.U_smo), self._slot("loss_smooth_obj"), rws_a, CL, NS,
-                                     sa), "smooth(obj)")
-            self.ev_smo.record(main)
-        if self.smooth_obj_on_main:
-            self._aux_block(it)
         if on["depth"] and on["sil"]:
             main.wait_event(self.ev_dgrad)       # d loss / d (object's depth image), from the side stream
             ctx_o = self.dctx[0]
@@ -934,7 +837,7 @@ class FusedStepper:
         # the object's smoothness gradient is formed INSIDE the rigid backward from the camera-space vertices the face setup
         # wrote (same floats as the unit gradient of the smoothness launch times its weight): on the step-1 sets this chain
         # then needs nothing from the side stream before the join - one cross-queue edge less on the iteration's tail
-        sm_in = on["smooth"] and on["sil"] and Vo <= 24576 and os.environ.get("HOMAN_SMOOTH_IN_RIGID", "1") != "0"
+        sm_in = on["smooth"] and on["sil"] and Vo <= 24576
         side_terms = on["con"] or (on["inter"] and sc_obj) or (on["smooth"] and not sm_in) or not on["sil"]
         if side_terms:
             main.wait_event(self.ev_pair)
@@ -957,17 +860,11 @@ class FusedStepper:
         it.sc_obj = sc_obj
 
     def _issue_join(self, it):
-        """tail: silhouette reduction (two streams), join, log row, scale gradients"""
-        (m, L, P, ck, B, Vo, on, w, CL, NS, C, main, side, sa, sctx, use_aux, log, sc_obj) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.w, it.CL, it.NS, it.C, it.main, it.side, it.sa, it.sctx, it.use_aux, it.log, it.sc_obj)
-        if not use_aux:
-            # two streams only: the silhouette reduction rides the tail of the silhouette chain (the shorter one at one
-            # clip), the log row follows the join
-            if on["sil"] and not self.sil_reduce_in_bwd:
-                ck(L.hm_sil_reduce_clips(B, Vo, sctx.F, sctx.S, P(m.keep_sum), self._slot("loss_sil_obj"), None,
-                                         P(sctx.workspace), CL, NS, sa), "sil_reduce")
+        """tail: join, log row (two streams), scale gradients"""
+        (m, L, P, ck, on, w, CL, C, main, side, sa, use_aux, log, sc_obj) = \
+            (it.m, it.L, it.P, it.ck, it.on, it.w, it.CL, it.C, it.main, it.side, it.sa, it.use_aux, it.log, it.sc_obj)
         main.wait_stream(side)               # join
-        if use_aux or (on["col"] and self.col_on_aux):
+        if use_aux:
             main.wait_stream(self.aux)
         elif log:
             ck(L.hm_log_total_clips(P(self.vals), P(self.weights), len(self.SLOTS), P(self.opt.step_t),
@@ -1002,11 +899,14 @@ class FusedStepper:
                               None, None, P(sctx.workspace), CL, None, NS, sctx.sum_log2q, sa), "sil_bwd")
 
     def _depth_render(self, verts, ctx, V_, sil, dep, stream_id):
-        """depth + silhouette images of one mesh at the full-image camera (reference homan.py:391,406), all frames"""
+        """depth + silhouette images of one mesh at the full-image camera (reference homan.py:391,406), all frames.  The
+        renders write into buffers this stepper owns and keeps passing: a region that is empty again leaves the empty pattern it
+        wrote last time alone (hm_sil_fwd's persistent_outputs, as the silhouette render does) - at the full-image camera nine
+        regions in ten are background"""
         m, L, P = self.model, self.L, _lib.ptr
         _lib.check(L.hm_sil_fwd(P(verts), P(ctx.faces), 0, P(m.camintr), self.B, V_, ctx.F, ctx.S, 1.0, self.ops.NMR_NEAR,
                                 self.ops.NMR_FAR, None, None, None, P(sil), None, P(ctx.work_order), P(dep), None, 0, None, None,
-                                None, 0, self.depth_persistent, P(ctx.workspace), stream_id), "depth render")
+                                None, 0, 1, P(ctx.workspace), stream_id), "depth render")
 
     def _adam_log(self):
         if not self.log_in_adam:

@@ -26,8 +26,6 @@ _SIGNATURES = {
     "hm_tune_raster_lds_pad": (_I, [_I]),
     "hm_tune_raster_reorder": (_I, [_I]),
     "hm_tune_nn_lds_pad": (_I, [_I]),
-    "hm_tune_lds_pad": (_I, [_I, _I]),
-    "hm_tune_rigid_chunked": (_I, [_I]),
     "hm_debug_sweep_caps": (_I, [_I]),
     "hm_shade_rgb": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _I, _VP, _F, _F, _VP, _VP, _VP, _VP]),
     "hm_rigid_bwd_sil": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _F, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
@@ -194,7 +192,7 @@ def check(rc, what):
         raise HomanAmdError(f"{what} failed with code {rc}")
 
 
-# Graphs are kept alive for the life of the process (HOMAN_KEEP_GRAPHS=0 switches that off).  ROCm 7.0's graph executor has
+# Graphs are kept alive for the life of the process.  ROCm 7.0's graph executor has
 # crashed in hip::Graph::UpdateStreams at the first replay of a NEW graph after several dozen graphs had been created AND
 # destroyed in the process - a test suite, or a fitting process that walks a dataset clip by clip, one stepper per clip.
 # Graphs that are never destroyed do not trigger it, and a captured graph here owns no large buffer (the steppers allocate
@@ -204,8 +202,7 @@ _KEPT_GRAPHS = []
 
 def new_graph():
     g = torch.cuda.CUDAGraph()
-    if os.environ.get("HOMAN_KEEP_GRAPHS", "1") != "0":
-        _KEPT_GRAPHS.append(g)
+    _KEPT_GRAPHS.append(g)
     return g
 
 

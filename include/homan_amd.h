@@ -12,8 +12,9 @@
  *   - all work is enqueued on `stream` and is asynchronous w.r.t. the host (capturable in a hipGraph), except
  *     hm_bench_raster_fwd and the hm_debug_* helpers;
  *   - return value: HM_OK (0) or a negative error code; nothing throws across the ABI;
- *   - re-entrant per (workspace, stream).  State outside the caller's buffers: the hm_tune_* LAUNCH HINTS (grid sizes / LDS
- *     ballast of a few kernels: scheduling only, never results), which are PER CALLING THREAD (thread-local) and read when an
+ *   - re-entrant per (workspace, stream).  State outside the caller's buffers: the four hm_tune_* LAUNCH HINTS (the edge
+ *     sweeps' grid, the rasteriser's LDS ballast and workgroup order, the metric-only search's LDS ballast: scheduling only,
+ *     never results), which are PER CALLING THREAD (thread-local) and read when an
  *     entry point is called or captured - a thread sets them, issues or captures its launches, restores them; threads do not
  *     see each other's values; and the process-wide hm_debug_* hooks (timing events, capacity overrides: test tools);
  *   - workspaces that hold a reduction ticket (hm_reduce_workspace_bytes, hm_sil_workspace_bytes,
@@ -58,10 +59,6 @@ int hm_rigid_bwd(const float* mesh, const float* rot6d, const float* scale, int 
 /* workspace of hm_rigid_bwd / hm_rigid_bwd_sil (zero-filled once; per-frame tickets reset themselves): with it the frame
  * is split over ceil(V/256) workgroups and the last one finishes; NULL = one workgroup per frame. */
 size_t hm_rigid_workspace_bytes(int N);
-/* Scheduling hint, no effect on results (exact sums): 1 = hm_rigid_bwd_sil* as ceil(V / 256) small workgroups per frame + a
- * per-frame ticket instead of one large workgroup per frame.  Per calling thread (thread-local), read at launch / capture; returns the previous
- * value; < 0 only queries. */
-int hm_tune_rigid_chunked(int enable);
 /* hm_rigid_bwd with the silhouette gradient as one more full term, gathered on the fly from the per-(face, corner) NDC
  * gradients of the edge sweeps (sil_parts = hm_sil_parts(workspace) after an hm_sil_bwd called with grad_verts == NULL;
  * adj_off / adj_items / cam_verts / K / orig_size / F as given to that call): no gather launch, no (N,V,3) round trip. */
@@ -236,10 +233,6 @@ int hm_tune_raster_reorder(int enable);
 /* Same for the metric-only nearest-vertex search (small latency-bound workgroups that otherwise take every wave slot of a CU
  * next to the kernel they overlap): 65536 = two search workgroups per CU. */
 int hm_tune_nn_lds_pad(int bytes);
-/* The same ballast for the other kernels of the hand side, by family: 0 MANO forward, 1 MANO backward, 2 the smoothness /
- * interaction / hand-terms launches, 3 the fused pair-terms launch, 4 rigid backward.  Returns the previous value (-1: no such
- * family); bytes < 0 only queries. */
-int hm_tune_lds_pad(int family, int bytes);
 /* test hook: cap > 0 shrinks the capacity tables of the sweep work list so that small inputs take the beyond-capacity
  * paths (binary search for a unit's first face, atomically accumulated faces); 0 restores the defaults.  Returns the
  * previous value. */

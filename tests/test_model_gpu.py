@@ -367,8 +367,8 @@ def test_adaptive_raster_order_is_invisible_to_the_results(mano_model, monkeypat
     from homan_amd.jointopt import FusedStepper
     name, steps = "ref_step2_cube_b4_s64", 10
     outs = []
-    for on in ("0", "1"):
-        monkeypatch.setenv("HOMAN_RASTER_REORDER", on)
+    for on in (0, 1):
+        monkeypatch.setattr(FusedStepper, "raster_reorder", on)
         rec, model, weights, meta = _build_hip(name, mano_model, sync=False)
         st = FusedStepper(model, weights, meta["lr"], steps)
         assert hl.lib().hm_tune_raster_reorder(-1) == 0          # (the hint is restored after the capture)

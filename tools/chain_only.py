@@ -1,6 +1,5 @@
 """What do the cross-queue edges of the fused iteration cost?  Steady-state microseconds per iteration of the cfg2 fit (and of
-cfg1 / one frame) for the shipped launch graph, for variants of its fork / join structure (environment switches of
-homan_amd/fused.py) and for two MEASUREMENT-ONLY launch graphs defined in this file as subclasses of FusedStepper: the silhouette
+cfg1 / one frame) for the shipped launch graph and for two MEASUREMENT-ONLY launch graphs defined in this file as subclasses of FusedStepper: the silhouette
 chain ALONE on one queue (no side stream at all, the hand does not move - a floor, not a fit), and both chains without any edge
 between them inside the four-iteration graph (not a fit either).  Same process, same box, steppers built one after the other.
 usage (GPU box): python tools/chain_only.py [cfg2 cfg1 b1]"""
@@ -74,15 +73,9 @@ class NoEdges(FusedStepper):
         main.wait_stream(self.side)
 
 
-VARIANTS = [("shipped", {}, FusedStepper), ("main_only", {}, ObjectChainOnly), ("no_edges", {}, NoEdges),
-            ("side_waits_for_setup", {"HOMAN_SIDE_OWN_VO": "0"}, FusedStepper), ("shipped_again", {}, FusedStepper)]
+VARIANTS = [("shipped", FusedStepper), ("main_only", ObjectChainOnly), ("no_edges", NoEdges), ("shipped_again", FusedStepper)]
 if os.environ.get("CHAIN_SKIP"):          # (A/B of library builds: the shipped graph and the one-queue floor only)
     VARIANTS = VARIANTS[:2]
-extra = os.environ.get("CHAIN_VARIANTS")          # "name:K=V,K=V;name2:K=V"
-if extra:
-    for item in extra.split(";"):
-        name, kv = item.split(":")
-        VARIANTS.append((name, dict(x.split("=") for x in kv.split(",")), FusedStepper))
 CONFIGS = dict(cfg1=(dict(frames=10, size=128, obj="cube"), synth.CFG1_LOSS_WEIGHTS),
                b1=(dict(frames=1, size=256, obj="bottle"), synth.CFG1_LOSS_WEIGHTS),
                cfg2=(dict(frames=30, size=256, obj="bottle"), synth.STEP1_LOSS_WEIGHTS),
@@ -95,20 +88,11 @@ for cname in (sys.argv[1:] or ["cfg2"]):
     clip = synth.make_clip(seed=0, frames=kw["frames"], rend_size=kw["size"], image_size=kw["size"], obj=kw["obj"],
                            silhouette_fn=sil_fn, hand_verts_fn=hand_fn)
     out[cname] = {}
-    for vname, env, cls in VARIANTS:
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            model = build_model(copy.deepcopy(clip["person_parameters"]), copy.deepcopy(clip["object_parameters"]),
-                                objvertices=clip["objvertices"], objfaces=clip["objfaces"], camintr=clip["camintr"],
-                                optimize_mano=True, image_size=kw["size"], mano_model=mano, rend_size=kw["size"], sync_metrics=False)
-            st = cls(model, dict(lw), 1e-2, 2000)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
+    for vname, cls in VARIANTS:
+        model = build_model(copy.deepcopy(clip["person_parameters"]), copy.deepcopy(clip["object_parameters"]),
+                            objvertices=clip["objvertices"], objfaces=clip["objfaces"], camintr=clip["camintr"],
+                            optimize_mano=True, image_size=kw["size"], mano_model=mano, rend_size=kw["size"], sync_metrics=False)
+        st = cls(model, dict(lw), 1e-2, 2000)
         st.run(400)
         torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -34,7 +34,6 @@ def main():
     lw = dict(synth.CFG1_LOSS_WEIGHTS if a.frames < 2 else synth.STEP1_LOSS_WEIGHTS)
     if a.depth:
         lw["lw_depth"] = 1.0
-    os.environ["HOMAN_GRAPH_ITERS"] = "1"
     st = FusedStepper(model, lw, 1e-2, a.warm + 8)
     L = _lib.lib()
     nwg = a.frames * 256
