@@ -81,6 +81,9 @@ _SIGNATURES = {
     "hm_collision_fwd": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _VP]),
     "hm_collision_read_grid": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
     "hm_collision_dist_values": (_I, [_VP, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "hm_cloud_metrics_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "hm_cloud_metrics": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "hm_align_stats": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "hm_adam_slot_bytes": (_SZ, []),
     "hm_adam_step": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP]),
     "hm_adam_step_log": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),

@@ -799,3 +799,36 @@ def collision_dist_values(vh, vo, cctx, scale_factor=0.2):
                                                        cctx.f1.shape[0], cctx.B, _lib.ptr(dv0), _lib.ptr(dv1),
                                                        _lib.ptr(cctx.ws), _lib.stream()), "hm_collision_dist_values")
     return {(1, 0): dv0, (0, 1): dv1}
+
+
+def cloud_metrics(x, y, aff_x=None, aff_y=None, per_point=False):
+    """Exact nearest neighbours between x (B,N,3) and y (B,M,3) in both directions (no grad; csrc/pointmetrics.hip) ->
+    (B,4) float64 {mean d2 x->y, mean d2 y->x, mean distance x->y, mean |x_i - y_i| (NaN when N != M)} and, per_point,
+    (x_d2 (B,N), x_idx (B,N) int32, y_d2 (B,M), y_idx (B,M) int32).  aff_x / aff_y (B,5) optional per-frame affine on load,
+    rows (cx, cy, cz, div, mul): p' = ((p - c) / div) * mul."""
+    x, y = _f32(x.detach()), _f32(y.detach())
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    dev = x.device
+    out4 = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    ws = torch.empty(_lib.lib().hm_cloud_metrics_workspace_bytes(B, N, M), dtype=torch.uint8, device=dev)
+    pp = (torch.empty(B, N, device=dev), torch.empty(B, N, dtype=torch.int32, device=dev),
+          torch.empty(B, M, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev)) if per_point else (None,) * 4
+    _lib.check(_lib.lib().hm_cloud_metrics(_lib.ptr(x), _lib.ptr(y), B, N, M, _lib.ptr(aff_x), _lib.ptr(aff_y),
+                                           *[_lib.ptr(t) for t in pp], _lib.ptr(out4), _lib.ptr(ws), _lib.stream()),
+               "hm_cloud_metrics")
+    return (out4, pp) if per_point else out4
+
+
+def align_stats(gt_hand, pred_hand, frames, pred_centroid_from_gt=True):
+    """Hand alignment of reference homan/eval/pointmetrics.py:61-90 (no grad): hands (frames*hands, V, 3), frame-major ->
+    aff_gt (frames,5), aff_pred (frames,5) (the cloud_metrics affines of the object search) and hand_mean (frames*hands)
+    float64, the mean vertex distance of the aligned hands."""
+    gt_hand, pred_hand = _f32(gt_hand.detach()), _f32(pred_hand.detach())
+    hands, V = gt_hand.shape[0] // frames, gt_hand.shape[1]
+    dev = gt_hand.device
+    aff_gt, aff_pred = torch.empty(frames, 5, device=dev), torch.empty(frames, 5, device=dev)
+    hand_mean = torch.empty(frames * hands, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().hm_align_stats(_lib.ptr(gt_hand), _lib.ptr(pred_hand), frames, hands, V, int(bool(pred_centroid_from_gt)),
+                                         _lib.ptr(aff_gt), _lib.ptr(aff_pred), _lib.ptr(hand_mean), _lib.stream()),
+               "hm_align_stats")
+    return aff_gt, aff_pred, hand_mean

@@ -294,6 +294,23 @@ int hm_nn_fwd(const float* verts_hand, const float* verts_obj, int B, int Vh, in
 int hm_contact_fwd(const float* verts_hand, const float* verts_obj, const int* nn_idx, int B, int Vh, int Vo,
                    float thresh, float* g_hand, float* g_obj, float* out1, void* workspace, hipStream_t stream);
 
+/* ------------------------------------------------------------------ evaluation point metrics
+ * reference homan/eval/pointmetrics.py:17-99 (pytorch3d chamfer_distance, scipy cKDTree): exact brute-force nearest
+ * neighbours between x (B,N,3) and y (B,M,3), both directions, d2 = (dx*dx + dy*dy) + dz*dz in fp32, ties to the lowest
+ * index.  aff_x / aff_y (B,5) optional per-frame affine applied on load: p' = ((p - c) / div) * mul, row (cx,cy,cz,div,mul).
+ * x_d2 / x_idx (B,N) and y_d2 / y_idx (B,M) optional per-point outputs.  out4 (B,4) double: mean d2 x->y, mean d2 y->x,
+ * mean distance x->y, mean |x_i - y_i| (NaN when N != M).  workspace: hm_cloud_metrics_workspace_bytes(B, N, M) bytes.
+ * A frame's values do not depend on the other frames of the call. */
+size_t hm_cloud_metrics_workspace_bytes(int B, int N, int M);
+int hm_cloud_metrics(const float* x, const float* y, int B, int N, int M, const float* aff_x, const float* aff_y, float* x_d2,
+                     int* x_idx, float* y_d2, int* y_idx, double* out4, void* workspace, hipStream_t stream);
+/* reference pointmetrics.py:61-90: hands (B*hands, V, 3), frame-major.  From the first hand of each frame: centroids and
+ * scales (double, rounded to fp32); pred_centroid_from_gt != 0 centres the prediction on the ground truth's centroid as the
+ * reference does (:68).  aff_gt (B,5) = (c_gt, 1, 1), aff_pred (B,5) = (c_pred, s_pred, s_gt) for hm_cloud_metrics;
+ * hand_mean (B*hands) double = mean vertex distance of the aligned hands. */
+int hm_align_stats(const float* gt_hand, const float* pred_hand, int B, int hands, int V, int pred_centroid_from_gt,
+                   float* aff_gt, float* aff_pred, double* hand_mean, hipStream_t stream);
+
 /* ------------------------------------------------------------------ SDF interpenetration
  * reference homan/lossutils.py:43-64 -> homan/interactions/scenesdf.py:77-148 and the `sdf` package (scenesdf.py:119).
  * Scene = {0: hand (closed faces), 1: object}.  out1[0] = sum of grid_sample(clamp(SDF_k,0), verts_l) over both

@@ -27,7 +27,7 @@ design and the current numbers; how the kernels got here - every measured step a
 | (f) rank 1 | object-pose initialisation (`pose_optimization.py:37-160,219-383`, `lib3d/optitrans.py:83-127`) | `homan_amd/pose_optimization.py` (`PoseOptimizer`, `find_optimal_pose`, and the clip-level `find_optimal_poses` of `:386-488` that `fit_vid_dataset.py:285-296` calls) over the same rasteriser run without anti-aliasing (`hm_sil_fwd` `alpha_full` with the masked L2 + IoU fused per sample, `hm_sil_bwd` modes 3 / 4 / 5); the default loop of `find_optimal_pose` is a fixed launch sequence without the autograd tape, run by a resident `PoseFitter` (`_FusedPoseLoop`: `hm_rigid_fwd` → `hm_offscreen_fwd` → raster → reduce → lines / sweeps → `hm_rigid_bwd_sil` → `hm_adam_step` → `hm_pose_keep_best`, one hipGraph), `mode="eager"` is the reference's loop verbatim; oracle `oracle/poseopt.py`; golden from the reference's own module (`tools/refharness/gen_goldens_poseinit.py`); `bench.py --pose-init` |
 | (f) rank 2 | hand silhouette term (`losses.py:166-181`) + ordinal depth (`homan.py:384-419`, `lossutils.py:133-169`), both present-but-disabled upstream | `Losses.compute_sil_loss_hand` (per-hand ROI render, own keep-mask normalisation; the reference body cannot run past its first frame, built for the evident intent) ; ordinal depth = row a19.  Oracle-pinned |
 | (f) rank 3 | textured / shaded renders for visualisation (`homan.py:168-219,510-628`, `visualize.py:44-128`, `meshutils.py:7-51`, `jointopt.py:158-176`) | rgb output of the rasteriser (`hm_shade_rgb`: NMR flat lighting on the forward's index map), `homan_amd/nmr.py` (`model.renderer`), `HOMan.render / render_gt / render_with_gt / render_limem / save_obj`, `homan_amd/{meshutils,visualize,trans3d}.py`, frames out of `optimize_hand_object`; oracle `oracle/nmr.py` (`lighting`, `shade_index_map`); `tests/test_render_gpu.py` |
-| (f) rank 4 | checkpoint / evaluation hand-off (`fit_vid_dataset.py:365-372,322-338`, `postprocess.py:16-77`, `eval/pointmetrics.py:102-124`) | `homan_amd/checkpoint.py` (`joint_fit.pt` contract, files interchange with the reference's), `homan_amd/pointmetrics.py::get_inter_metrics` on `hm_collision_fwd` + `hm_collision_dist_values` (per-vertex penetration depths = `sdf_meta["dist_values"]`) |
+| (f) rank 4 | checkpoint / evaluation hand-off (`fit_vid_dataset.py:365-372,322-338`, `postprocess.py:16-77`, `eval/pointmetrics.py:17-124`) | `homan_amd/checkpoint.py` (`joint_fit.pt` contract, files interchange with the reference's), `homan_amd/pointmetrics.py::get_inter_metrics` on `hm_collision_fwd` + `hm_collision_dist_values` (per-vertex penetration depths = `sdf_meta["dist_values"]`); `get_point_metrics` / `get_align_metrics` (chamfer, ADD-S, vertex and hand-aligned errors) on `hm_cloud_metrics` (exact two-way nearest neighbours, `csrc/pointmetrics.hip`) + `hm_align_stats` |
 
 ## 1. The path and its boundary
 
@@ -514,8 +514,8 @@ against them like against the single-hand goldens.
 
 ## 7. Out of scope (and why)
 
-Evidence extraction (detectron2 / FrankMocap networks), datasets, tracking, dataset-level evaluation (chamfer / ADD-S on
-ground truth, codalab dumps), html / video export: SURVEY §8 marks them out of the hot path and their inputs (weights,
+Evidence extraction (detectron2 / FrankMocap networks), datasets, tracking, dataset-level evaluation (codalab dumps),
+html / video export: SURVEY §8 marks them out of the hot path and their inputs (weights,
 data) are not available.  `contact_mode≠dist_tanh`: non-default branches of a file the reference never reaches.  `hand_proj_mode="ortho"`
 (`homan/homan.py:364-371` -> `utils/camera.py:59-105`, non-default) IS built since round 5 - `HOMan.get_verts_hand` places the
 hand by its scaled-orthographic camera `cams_hand` (identity rotation, translation from the camera, `s (v + t)` on the rigid
