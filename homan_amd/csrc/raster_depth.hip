@@ -137,15 +137,17 @@ __global__ void k_depth_bwd_gather(const float* __restrict__ gf9, const int* __r
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gflags) {
         // a frame without any flagged segment (see k_depth_bwd_faces) has gf9 == 0 throughout: its vertices get their zeros
-        // without the two dependent round trips of the gather.  The workgroup scans the flag bytes of the (one or two) frames
-        // its vertices belong to.
+        // without the two dependent round trips of the gather.  The workgroup scans the flag bytes of the frames its vertices
+        // belong to, up to eight of them; a workgroup that spans more (small meshes: V < 37) gathers every vertex - s_any has
+        // eight entries and is not consulted then.
         __shared__ int s_any[8];
         const long nv = (long)B * V;
         const int b_lo = (int)(((long)blockIdx.x * blockDim.x) / V);
         const int b_hi = (int)(min((long)blockIdx.x * blockDim.x + blockDim.x - 1, nv - 1) / V);
-        if (threadIdx.x < 8) s_any[threadIdx.x] = b_hi - b_lo >= 8 ? 1 : 0;
+        const bool scan = b_hi - b_lo < 8;                                // (block-uniform)
+        if (threadIdx.x < 8) s_any[threadIdx.x] = 0;
         __syncthreads();
-        if (b_hi - b_lo < 8) {
+        if (scan) {
             const int nflag = S * (S >> 6);                               // bytes per frame, a multiple of 64
             for (int bb = b_lo; bb <= b_hi; ++bb) {
                 unsigned a = 0u;
@@ -156,7 +158,7 @@ __global__ void k_depth_bwd_gather(const float* __restrict__ gf9, const int* __r
         }
         __syncthreads();
         if (i >= nv) return;
-        if (!s_any[(int)(i / V) - b_lo]) {
+        if (scan && !s_any[(int)(i / V) - b_lo]) {
             grad_verts[3 * i] = 0.f; grad_verts[3 * i + 1] = 0.f; grad_verts[3 * i + 2] = 0.f;
             return;
         }
@@ -226,7 +228,10 @@ __global__ __launch_bounds__(256) void k_ordinal_depth(const float* __restrict__
     const int b = blockIdx.y;
     const long base = (long)b * S * S;
     const int per = (S * S + ORD_CHUNKS - 1) / ORD_CHUNKS, i0 = blockIdx.x * per, i1 = min(S * S, i0 + per);
-    float c00 = 0.f, c11 = 0.f, c01 = 0.f, ms01 = 0.f, s01 = 0.f, ms10 = 0.f, s10 = 0.f;
+    float c00 = 0.f, c11 = 0.f, c01 = 0.f, ms01 = 0.f, ms10 = 0.f;
+    // a thread's softplus sums in double: up to 256 float additions one after the other drift when the terms are alike (a fully
+    // covered frame with every difference clamped adds the same number 256 times, and its rounding with it: 1e-6 of the sum)
+    double s01 = 0.0, s10 = 0.0;
     // four of a thread's pixels per trip, all six words of each requested before the first is looked at: 4 dependent round
     // trips per thread where the pixel-by-pixel walk (alpha -> test -> depths and masks -> test) had 32.  Same pixels in the
     // same order per thread: the same sums.
@@ -247,12 +252,12 @@ __global__ __launch_bounds__(256) void k_ordinal_depth(const float* __restrict__
                 c01 += 1.f;
                 const float z0 = zv0[u], z1 = zv1[u];
                 const bool g0 = mv0[u] != 0, g1 = mv1[u] != 0;
-                if (g0 && !g1 && z1 < z0) { ms01 += 1.f; s01 += logf(1.0f + expf(fminf(fmaxf(z0 - z1, 0.f), 2.f))); }
-                if (g1 && !g0 && z0 < z1) { ms10 += 1.f; s10 += logf(1.0f + expf(fminf(fmaxf(z1 - z0, 0.f), 2.f))); }
+                if (g0 && !g1 && z1 < z0) { ms01 += 1.f; s01 += (double)logf(1.0f + expf(fminf(fmaxf(z0 - z1, 0.f), 2.f))); }
+                if (g1 && !g0 && z0 < z1) { ms10 += 1.f; s10 += (double)logf(1.0f + expf(fminf(fmaxf(z1 - z0, 0.f), 2.f))); }
             }
         }
     }
-    float v[7] = {c00, c11, c01, ms01, s01, ms10, s10};
+    float v[7] = {c00, c11, c01, ms01, (float)s01, ms10, (float)s10};
     hm_block_sum_n<7>(v, red);           // (two barriers for the seven sums; the combination order of hm_block_sum)
     unsigned long long* fr = reinterpret_cast<unsigned long long*>(frame_part) + (long)b * 4;
     // the frame's record; its word 1 also counts the chunks that have arrived (bits 42..), so the chunk that completes a frame
@@ -324,11 +329,11 @@ __global__ void k_ordinal_depth_bwd(const float* __restrict__ d0, const float* _
         const float up = upstream[0] / rec[0];
         if (b0 && !b1 && z1 < z0 && rec[1] > 0.f) {
             const float x = z0 - z1;
-            if (x > 0.f && x < 2.f) { const float sg = hm_sigmoid(x); r0 += up * sg / rec[1]; r1 -= up * sg / rec[1]; }
+            if (x > 0.f && x <= 2.f) { const float sg = hm_sigmoid(x); r0 += up * sg / rec[1]; r1 -= up * sg / rec[1]; }
         }
         if (b1 && !b0 && z0 < z1 && rec[3] > 0.f) {
             const float x = z1 - z0;
-            if (x > 0.f && x < 2.f) { const float sg = hm_sigmoid(x); r1 += up * sg / rec[3]; r0 -= up * sg / rec[3]; }
+            if (x > 0.f && x <= 2.f) { const float sg = hm_sigmoid(x); r1 += up * sg / rec[3]; r0 -= up * sg / rec[3]; }
         }
     }
     g0[i] = r0;

@@ -790,11 +790,11 @@ void orc_ordinal_depth_grad(const float *d0, const float *d1, const uint8_t *a0,
             const float up = upstream / t0;
             if (m0[i] && !m1[i] && z1 < z0 && t1 > 0.f) {
                 const float x = z0 - z1;
-                if (x > 0.f && x < 2.f) { const float sg = oc_sigmoid(x); r0 += up * sg / t1; r1 -= up * sg / t1; }
+                if (x > 0.f && x <= 2.f) { const float sg = oc_sigmoid(x); r0 += up * sg / t1; r1 -= up * sg / t1; }
             }
             if (m1[i] && !m0[i] && z0 < z1 && t3 > 0.f) {
                 const float x = z1 - z0;
-                if (x > 0.f && x < 2.f) { const float sg = oc_sigmoid(x); r1 += up * sg / t3; r0 -= up * sg / t3; }
+                if (x > 0.f && x <= 2.f) { const float sg = oc_sigmoid(x); r1 += up * sg / t3; r0 -= up * sg / t3; }
             }
         }
         g0[i] = r0; g1[i] = r1;

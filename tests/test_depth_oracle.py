@@ -8,6 +8,7 @@ import torch
 
 from oracle import model as o_model
 from oracle import nmr
+from tests import util
 
 
 def _two_triangles():
@@ -70,3 +71,72 @@ def test_ordinal_depth_loss_counts_pairs_like_the_reference():
     # pairs: (0,0): 2 frames, (1,1): 2 frames, (0,1) and (1,0): frame 1 only -> 6
     want = np.log1p(np.exp(0.1)) / 6.0
     assert abs(float(out) - want) < 1e-6
+
+
+# ------------------------------------------------------------------ the float64 references of tests/util.py vs the oracle
+def _oracle_ordinal(sc):
+    d = [torch.from_numpy(x).clone().requires_grad_(True) for x in sc["d"]]
+    masks = torch.stack([torch.from_numpy(x) != 0 for x in sc["m"]], 1)
+    loss = o_model.compute_ordinal_depth_loss(masks, [torch.from_numpy(x) == 1 for x in sc["a"]], d)["loss_depth"]
+    if loss.requires_grad and bool(torch.isfinite(loss)):
+        loss.backward()
+    return loss.detach(), [x.grad if x.grad is not None else torch.zeros_like(x) for x in d]
+
+
+def test_ordinal_depth_ref_matches_the_oracle():
+    """util.ordinal_depth_ref (float64) against oracle.model.compute_ordinal_depth_loss (float32) on every synthetic clip the
+    GPU tests use: value and both gradient images.  The largest deviation is the float32 noise floor util.E32_ORDINAL."""
+    worst = 0.0
+    for B, S, kind in util.ORDINAL_CASES + [(6, 64, "three_layers")]:
+        sc = util.ordinal_scene3(B, S) if kind == "three_layers" else util.ordinal_scene(B, S, kind)
+        if kind != "full_clamped":
+            util.assert_ordinal_scene_has_no_near_ties(sc)
+        want, gw = util.ordinal_ref_on_scene(sc)
+        got, gg = _oracle_ordinal(sc)
+        assert float(want) > 0
+        devs = [util.deviation(got.numpy(), want.numpy())] + [util.deviation(a.numpy(), b.numpy()) for a, b in zip(gg, gw)]
+        print(f"ordinal B={B} S={S} {kind}: loss {float(want):.9g} e32 value {devs[0]:.3e} gradients", *(f"{x:.3e}" for x in devs[1:]))
+        assert (kind == "full_clamped") == (not gw[0].any())          # clamped everywhere: no gradient at all
+        for a, b in zip(gg, gw):                                       # the same pixels carry a gradient (the bounds included)
+            assert torch.equal(a != 0, b != 0)
+        worst = max(worst, *devs)
+    assert 0.5 * util.E32_ORDINAL < worst <= util.E32_ORDINAL, worst
+
+
+def test_ordinal_depth_ref_at_the_clamp_bounds_and_without_pairs():
+    """Row 0 of a mixed scene holds x = ORD_BOUND_X in turn: torch's clamp passes the gradient for 0 < x <= 2 (bounds inclusive,
+    x = 0 is not wrongly ordered), reference and oracle alike; a clip without a covered pixel gives 0 / 0 in both."""
+    sc = util.ordinal_scene(1, 64, "mixed")
+    _, gw = util.ordinal_ref_on_scene(sc)
+    _, gg = _oracle_ordinal(sc)
+    x = np.asarray(util.ORD_BOUND_X, np.float32)[np.arange(64) % len(util.ORD_BOUND_X)]
+    want_nz = torch.from_numpy((x > 0) & (x <= 2))
+    assert want_nz[3] and x[3] == 2.0                                  # x == 2.0 exactly carries a gradient
+    for g in (gw, gg):
+        assert torch.equal(g[0][0, 0] > 0, want_nz) and torch.equal(g[1][0, 0] < 0, want_nz)
+        assert torch.equal(g[1][0, 1] > 0, want_nz) and torch.equal(g[0][0, 1] < 0, want_nz)
+    sc = util.ordinal_scene(4, 64, "no_pairs")
+    assert torch.isnan(util.ordinal_ref_on_scene(sc)[0]) and torch.isnan(_oracle_ordinal(sc)[0])
+
+
+def test_depth_backward_ref_matches_the_oracle():
+    """util.depth_backward_ref (float64) against the oracle's depth-image backward (projection + _RasterizeAlphaDepth, float32)
+    over the mesh x size grid of the GPU test, for a dense, a banded and (small meshes) a late-frames upstream image.  The largest
+    deviation is the float32 noise floor util.E32_DEPTH_BWD."""
+    worst = 0.0
+    for dims, (V, B) in util.DEPTH_BWD_MESHES.items():
+        for S in util.DEPTH_BWD_SIZES:
+            for near in ((False, True) if V == 8 and S > 64 else (False,)):
+                verts, faces, K = util.depth_bwd_scene(dims, B, near)
+                assert verts.shape[1] == V
+                for pat in ("dense", "band", "late_frames"):
+                    g = util.depth_bwd_upstream(pat, B, S, V)
+                    if g is None or (pat == "late_frames" and S == 256):
+                        continue
+                    got, f9, idx = util.oracle_depth_backward(verts, faces, K, S, g)
+                    want = util.depth_backward_ref(f9, idx, g, faces, verts.numpy(), K.numpy(), 1.0)
+                    assert np.abs(want).max() > 0
+                    dev = util.deviation(got, want)
+                    print(f"depth bwd V={V} B={B} S={S} near={near} {pat}: e32 {dev:.3e}")
+                    worst = max(worst, dev)
+    assert 0.5 * util.E32_DEPTH_BWD < worst <= util.E32_DEPTH_BWD, worst
