@@ -84,6 +84,9 @@ _SIGNATURES = {
     "hm_cloud_metrics_workspace_bytes": (_SZ, [_I, _I, _I]),
     "hm_cloud_metrics": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "hm_align_stats": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "hm_mask_crop_resize": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP]),
+    "hm_target_masks": (_I, [_I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP]),
+    "hm_instance_masks": (_I, [_VP, _I, _I, _I, _VP, _I, _VP, _VP]),
     "hm_adam_slot_bytes": (_SZ, []),
     "hm_adam_step": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP]),
     "hm_adam_step_log": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),

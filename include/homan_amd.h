@@ -311,6 +311,36 @@ int hm_cloud_metrics(const float* x, const float* y, int B, int N, int M, const 
 int hm_align_stats(const float* gt_hand, const float* pred_hand, int B, int hands, int V, int pred_centroid_from_gt,
                    float* aff_gt, float* aff_pred, double* hand_mean, hipStream_t stream);
 
+/* ------------------------------------------------------------------ mask crops and target masks
+ * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
+ * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
+ * binarised as `!= 0`, in fp32, then >= 0.5.  masks (N,H,W): bytes (masks_f32 == 0) or fp32 (masks_f32 != 0); index (R) int32
+ * = the mask of each ROI (NULL: ROI r crops mask r; an entry outside [0, N) gives an empty crop); boxes (R,4) fp32
+ * x1 y1 x2 y2 in pixels; out (R,S,S) bytes 0 / 1.  Every operation is rounded to fp32 and the samples of an output pixel
+ * are summed in one lane, rows then columns: the decision at an exact 0.5 tie is that of a scalar loop in that order.
+ * R == 0 is HM_OK and launches nothing; S <= 0 and non-positive N, H, W are HM_ERR_BAD_ARG. */
+int hm_mask_crop_resize(const void* masks, int masks_f32, int N, int H, int W, const int* index, const float* boxes, int R,
+                        int S, unsigned char* out, hipStream_t stream);
+/* The -1 / 0 / 1 fp32 targets of R ROIs in one launch, pixel for pixel the composition of hm_mask_crop_resize calls.
+ *   mode 0, hand (reference maskutils.py:61-65 add_target_hand_occlusions): t = crop(target), then -1 wherever a cropped
+ *     occluder is set (the occluder wins);
+ *   mode 1, object (maskutils.py:29-36 add_occlusions): target (Nt,S,S) is cropped already; -1 wherever a cropped occluder
+ *     is set, then 1 wherever the target is set (the object wins);
+ *   mode 2, ground-truth masks (prepare/gtmasks.py:105-107): crop(target) - (any cropped occluder).
+ * target (Nt,H,W) (mode 1: (Nt,S,S)) and occluders (No,H,W): bytes or fp32 as above; target_index (R) as `index` above;
+ * occluder_index (R,K) int32: the occluder masks of each ROI, entries outside [0, No) are skipped (K == 0: no occluder,
+ * the occluder pointers may be NULL); out (R,S,S) fp32. */
+int hm_target_masks(int mode, const void* target, int target_f32, int Nt, const int* target_index, const void* occluders,
+                    int occluders_f32, int No, const int* occluder_index, int K, int H, int W, const float* boxes, int R, int S,
+                    float* out, hipStream_t stream);
+/* Per-instance visibility off the face-index map of a render (hm_sil_read_idx_map: (B,2S,2S) int32): `renders[:, i]` of
+ * reference prepare/gtmasks.py:77-92 (one-hot face colours, ambient light 1, directional 0) without the (B,3,S,S) float
+ * image.  face_start: HOST int[I + 1], instance i owns faces [face_start[i], face_start[i+1]) (I <= 8, else
+ * HM_ERR_UNSUPPORTED); out (B,I,S,S) bytes = how many of the pixel's 2x2 samples the instance owns: count / 4 is the
+ * anti-aliased render value, count > 0 the instance mask. */
+int hm_instance_masks(const int* idx_map, int B, int S, int F, const int* face_start, int I, unsigned char* out,
+                      hipStream_t stream);
+
 /* ------------------------------------------------------------------ SDF interpenetration
  * reference homan/lossutils.py:43-64 -> homan/interactions/scenesdf.py:77-148 and the `sdf` package (scenesdf.py:119).
  * Scene = {0: hand (closed faces), 1: object}.  out1[0] = sum of grid_sample(clamp(SDF_k,0), verts_l) over both
