@@ -9,6 +9,8 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+HEADER = os.path.join(INCLUDE, "homan_amd.h")       # the C ABI: compiled into every unit, parsed by lib.py
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libhoman_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -24,7 +26,7 @@ def is_stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h"))
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -32,7 +34,7 @@ def build_lib(force=False, verbose=False):
     if not force and not is_stale():
         return LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [HIPCC] + FLAGS + ["-I", CSRC, "-o", LIB_PATH] + sources()
+    cmd = [HIPCC] + FLAGS + ["-I", CSRC, "-I", INCLUDE, "-o", LIB_PATH] + sources()
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)

@@ -2,11 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define HM_OK 0
-#define HM_ERR_BAD_ARG (-1)
-#define HM_ERR_LAUNCH (-2)
-#define HM_ERR_UNSUPPORTED (-3)
+#include "homan_amd.h"      // the C ABI: HM_OK / HM_ERR_*, HmSilRender and the prototype every exported definition is held to
 
 #define HM_WAVE 64
 

@@ -101,15 +101,7 @@ HM_INTERNAL void hm_launch_setup_faces(const SilWs& w, const float* verts, const
                                        int faces_bstride, int B, int V, int F, int is, int* bins, const float* rigid_rot6d,
                                        const float* rigid_trans, const float* rigid_scale, int rigid_abs, int clip_len,
                                        float* cam_verts_out, hipStream_t stream);
-#define HM_MAX_RENDERS 4      // renders of one hm_sil_fwd_multi launch pair
-// one render of hm_sil_fwd_multi: the layout include/homan_amd.h declares (hm_sil_render_bytes() lets a binding check its own)
-struct HmSilRender {
-    const float* verts; const int* faces; const float* K; const float* keep; const float* ref; float* pooled;
-    const int* work_order; float* pooled_depth; const float* rigid_rot6d; const float* rigid_trans; const float* rigid_scale;
-    float* cam_verts_out; void* workspace;
-    int faces_bstride, B, V, F, S, mask_shared, rigid_abs, persistent_outputs, clip_len;
-    float orig_size, znear, zfar;
-};
+#define HM_MAX_RENDERS 4      // renders of one hm_sil_fwd_multi launch pair (HmSilRender: include/homan_amd.h)
 struct SetupFacesArgs {
     const float* verts; const float* K; float orig_size; const int* faces; int faces_bstride; int B, V, F, is; int* bins;
     const float* rigid_rot6d; const float* rigid_trans; const float* rigid_scale; int rigid_abs; int clip_len; float* cam_verts_out;

@@ -5,6 +5,7 @@ module raises.  Device pointers come from torch tensors (plumbing only: memory +
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -12,130 +13,64 @@ from . import build as _build
 
 _LIB = None
 _VP, _I, _F, _SZ, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
-
-# name -> (restype, argtypes)
-_SIGNATURES = {
-    "hm_sil_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "hm_sil_fwd": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _I, _F, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP,
-                        _VP, _I, _I, _VP, _VP]),
-    "hm_sil_parts": (_VP, [_VP, _I, _I, _I, _I]),
-    "hm_sil_fwd_multi": (_I, [_VP, _I, _I, _VP]),
-    "hm_sil_render_bytes": (_SZ, []),
-    "hm_sil_hint_near_winding": (_I, [_VP, _I, _VP]),
-    "hm_tune_sweep_blocks": (_I, [_I]),
-    "hm_tune_raster_lds_pad": (_I, [_I]),
-    "hm_tune_raster_reorder": (_I, [_I]),
-    "hm_tune_nn_lds_pad": (_I, [_I]),
-    "hm_debug_sweep_caps": (_I, [_I]),
-    "hm_shade_rgb": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _I, _VP, _F, _F, _VP, _VP, _VP, _VP]),
-    "hm_rigid_bwd_sil": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _F, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
-    "hm_sil_reduce": (_I, [_I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
-    "hm_depth_bwd": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_depth_bwd_sparse": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_ordinal_depth_bwd_flags": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_ordinal_depth_fwd": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
-    "hm_ordinal_depth_bwd": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
-    "hm_sil_bwd": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
-    "hm_bench_sil_kernels": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
-                                  _I, _VP, _VP]),
-    "hm_sil_read_boxes": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_debug_occupancy": (_I, [_VP, _VP]),
-    "hm_debug_sil_timing": (_I, [_I]),
-    "hm_sil_timestamps_bytes": (_SZ, [_I, _I, _I, _I]),
-    "hm_sil_timestamps": (_I, [_VP, _I, _I, _I, _I, _I, _VP]),
-    "hm_sil_timestamps_save": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_sil_timestamps_read": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP]),
-    "hm_debug_sil_timing_read": (_I, [_VP]),
-    "hm_debug_read_partials": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_sil_read_idx_map": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_sil_read_faces9": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_sil_read_parts": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
-    "hm_sil_invalidate_outputs": (_I, [_VP, _I, _I, _I, _I, _VP]),
-    "hm_rigid_fwd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
-    "hm_rigid_bwd": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_rigid_workspace_bytes": (_SZ, [_I]),
-    "hm_scale_by": (_I, [_VP, _VP, _L, _VP, _VP]),
-    "hm_scale2_by": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP]),
-    "hm_lincomb4": (_I, [_VP, _F, _VP, _F, _VP, _F, _VP, _F, _L, _VP, _VP]),
-    "hm_sum_small": (_I, [_VP, _I, _F, _VP, _F, _VP, _VP]),
-    "hm_log_total": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP]),
-    "hm_mano_fwd": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_mano_state_bytes": (_SZ, [_I]),
-    "hm_mano_workspace_bytes": (_SZ, [_I]),
-    "hm_mano_bwd": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_mano_bwd_rigid_clips": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I,
-                                     _VP, _VP, _I, _F, _VP, _VP, _I, _VP]),
-    "hm_reduce_workspace_bytes": (_SZ, []),
-    "hm_v2d_fwd": (_I, [_VP, _VP, _I, _VP, _F, _I, _I, _VP, _VP, _VP, _VP]),
-    "hm_smooth_fwd": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
-    "hm_priors_fwd": (_I, [_VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_hand_terms_fwd": (_I, [_VP, _VP, _I, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_pose_keep_best": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_pose_keep_best_log": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    "hm_offscreen_fwd": (_I, [_VP, _VP, _I, _I, _F, _F, _VP, _VP, _VP]),
-    "hm_inter_fwd": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _VP, _VP, _VP, _VP]),
-    "hm_inter_bwd": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
-    "hm_nn_fwd": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
-    "hm_contact_fwd": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _VP]),
-    "hm_collision_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
-    "hm_collision_fwd": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _VP]),
-    "hm_collision_read_grid": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
-    "hm_collision_dist_values": (_I, [_VP, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
-    "hm_cloud_metrics_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "hm_cloud_metrics": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_align_stats": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
-    "hm_mask_crop_resize": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP]),
-    "hm_target_masks": (_I, [_I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP]),
-    "hm_instance_masks": (_I, [_VP, _I, _I, _I, _VP, _I, _VP, _VP]),
-    "hm_adam_slot_bytes": (_SZ, []),
-    "hm_adam_step": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP]),
-    "hm_adam_step_log": (_I, [_VP, _I, _VP, _F, _F, _F, _I, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),
-    "hm_log_scalars": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
-    # clip batches (C clips, one launch per kernel): the plain signatures + clip_len [+ out_stride]
-    "hm_rigid_fwd_clips": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I, _VP]),
-    "hm_rigid_bwd_clips": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
-    "hm_rigid_bwd_sil_clips": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _F, _I, _I, _I, _VP, _VP, _VP,
-                                    _VP, _I, _I, _VP, _F, _VP]),
-    "hm_sum_small_clips": (_I, [_VP, _I, _F, _VP, _F, _VP, _I, _VP]),
-    "hm_mano_fwd_clips": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
-    "hm_mano_fwd_rows": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
-    "hm_mano_bwd_rows": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_sil_fwd_clips": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _I, _F, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP,
-                              _VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP]),
-    "hm_sil_fwd_phase_clips": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _I, _F, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP,
-                                    _VP, _VP, _I, _I, _VP, _I, _I, _VP, _I, _VP]),
-    "hm_sil_reduce_clips": (_I, [_I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_sil_bwd_clips": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I, _I, _VP]),
-    "hm_sil_bwd_phase_clips": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I, _I,
-                                    _I, _VP]),
-    "hm_v2d_fwd_clips": (_I, [_VP, _VP, _I, _VP, _F, _I, _I, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_smooth_fwd_clips": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_priors_fwd_clips": (_I, [_VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_hand_terms_fwd_clips": (_I, [_VP, _VP, _I, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP,
-                                     _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_pair_terms_fwd_clips": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP,
-                                     _VP, _F, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
-                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_inter_fwd_clips": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_nn_fwd_clips": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
-    "hm_nn_fwd_rigid_clips": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "hm_contact_fwd_clips": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_collision_fwd_clips": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP, _I, _I, _VP]),
-    "hm_log_total_clips": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _VP]),
-}
+# The closed type tables of the header: what is passed by value, and what a pointer (always a c_void_p here) may point to.
+_BY_VALUE = {"int": _I, "float": _F, "long": _L, "size_t": _SZ, "hipStream_t": _VP}
+_POINTEES = {"void", "float", "double", "int", "unsigned char", "HmSilRender"}
 
 
 class HomanAmdError(RuntimeError):
     pass
 
 
+def _ctype(decl, named=True):
+    """'const float* const* g_terms' -> (c_void_p, 'g_terms'); 'size_t' with named=False (a return type) -> (c_size_t, None).
+    A type outside the two tables raises: nothing defaults to int."""
+    words = decl.replace("*", " * ").split()
+    name = words.pop() if named and words else None
+    base = " ".join(w for w in words if w not in ("*", "const"))
+    if (named and not (name or "").isidentifier()) or base not in (_POINTEES if "*" in words else _BY_VALUE):
+        raise HomanAmdError(f"include/homan_amd.h: no ctypes mapping for `{decl.strip()}`")
+    return (_VP if "*" in words else _BY_VALUE[base]), name
+
+
+def parse_header(text):
+    """The ABI as include/homan_amd.h spells it -> ({name: (restype, argtypes)}, [(field of HmSilRender, ctype)]).
+    Strict: once comments, preprocessor lines and the extern "C" braces are gone, every statement must be the hipStream_t
+    typedef, the HmSilRender struct or an hm_* prototype over the types of _ctype; anything else raises HomanAmdError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'extern "C" \{(.*)\}', r"\1", text, flags=re.S)
+    sigs, fields = {}, []
+
+    def take_struct(m):
+        for decl in filter(str.strip, m.group(1).split(";")):
+            first, *more = decl.split(",")                   # `int B, V, F`: by-value members only
+            ctype, name = _ctype(first)
+            names = [name] + [n.strip() for n in more]
+            if more and (ctype is _VP or not all(n.isidentifier() for n in names)):
+                raise HomanAmdError(f"include/homan_amd.h: member list `{decl.strip()}` not understood")
+            fields.extend((n, ctype) for n in names)
+        return ""
+    text = re.sub(r"typedef struct HmSilRender \{(.*?)\} HmSilRender;", take_struct, text, flags=re.S)
+    for stmt in filter(str.strip, text.split(";")):
+        if stmt.split() == ["typedef", "struct", "ihipStream_t*", "hipStream_t"]:
+            continue
+        m = re.fullmatch(r"\s*(.+?)\b(hm_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if not m or m.group(2) in sigs:
+            raise HomanAmdError(f"include/homan_amd.h: statement `{stmt.strip()}` not understood")
+        params = m.group(3).strip()
+        sigs[m.group(2)] = (_ctype(m.group(1), named=False)[0],
+                            [] if params == "void" else [_ctype(p)[0] for p in params.split(",")])
+    return sigs, fields
+
+
 class SilRender(ctypes.Structure):
     """HmSilRender of include/homan_amd.h: one render of hm_sil_fwd_multi (fields as the arguments of hm_sil_fwd_clips)"""
-    _fields_ = ([(k, _VP) for k in ("verts", "faces", "K", "keep", "ref", "pooled", "work_order", "pooled_depth", "rigid_rot6d",
-                                    "rigid_trans", "rigid_scale", "cam_verts_out", "workspace")]
-                + [(k, _I) for k in ("faces_bstride", "B", "V", "F", "S", "mask_shared", "rigid_abs", "persistent_outputs",
-                                     "clip_len")]
-                + [(k, _F) for k in ("orig_size", "znear", "zfar")])
+
+
+# name -> (restype, argtypes), and the struct's members: read off the header, the one place that spells the ABI
+with open(_build.HEADER) as _fh:
+    _SIGNATURES, SilRender._fields_ = parse_header(_fh.read())
 
 
 def sil_renders(renders):

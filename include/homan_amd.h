@@ -203,7 +203,7 @@ int hm_depth_bwd_sparse(const float* verts, const float* K, int B, int V, int F,
                         const unsigned char* gflags, void* workspace, hipStream_t stream);
 /* Ordinal depth loss between two rendered layers (0 = object, 1 = hand): reference homan/homan.py:384-419 +
  * homan/lossutils.py:133-169 (as the method intends; the reference call site raises before reaching it, DESIGN.md).
- * d*/a*: depth / silhouette renders (B,S,S) f32; m*: instance masks (B,S,S) u8.  frame_part: B*8 floats (8-byte aligned),
+ * d0, d1 / a0, a1: depth / silhouette renders (B,S,S) f32; m0, m1: instance masks (B,S,S) u8.  frame_part: B*8 floats (8-byte aligned),
  * ZERO-filled once by the caller (per-frame integer records of the chunk workgroups; the call leaves them zero again);
  * rec: 5 floats {num_pairs, n01, sum01, n10, sum10} kept for the backward; out1[0] = loss.
  * workspace: the reduce workspace (see the small losses below), zero-filled once. */

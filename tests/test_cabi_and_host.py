@@ -1,5 +1,5 @@
-"""CPU-only checks: the C-ABI library loads and exports every symbol include/homan_amd.h declares, the ctypes table
-matches the header, and the host-side logic (collation, Adam groups, assets, generator, adjacency, sharding)."""
+"""CPU-only checks: the C-ABI library loads and exports every symbol include/homan_amd.h declares, the header compiles
+alone as C and C++, the ctypes table derived from it matches hand-written signatures, and the host-side logic (collation, Adam groups, assets, generator, adjacency, sharding)."""
 import ctypes
 import os
 import pickle
@@ -29,8 +29,49 @@ def test_library_exports_every_declared_symbol():
     assert sorted(lib.exported_symbols()) == declared, set(lib.exported_symbols()) ^ set(declared)
 
 
-def test_ctypes_arity_matches_header():
+def test_header_compiles_alone_as_c_and_cxx(tmp_path):
+    """The contract is usable as the only include of a C99 host and of a C++ one (no comment that ends early, no type it does
+    not declare itself)."""
+    import shutil
+    import subprocess
+    from homan_amd import build
+    unit = '#include "homan_amd.h"\nint main(void) { return HM_OK; }\n'
+    inc = os.path.join(ROOT, "include")
+    (tmp_path / "host.cpp").write_text(unit)
+    r = subprocess.run([build.HIPCC, "-fsyntax-only", "-x", "c++", "-Wall", "-Wextra", "-Werror", "-I", inc,
+                        str(tmp_path / "host.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    cc = shutil.which("cc")
+    if cc is None:
+        pytest.skip("no host C compiler (cc) on this machine; the C++ half ran")
+    (tmp_path / "host.c").write_text(unit)
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-I", inc,
+                        str(tmp_path / "host.c")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_ctypes_table_matches_header():
+    """lib._SIGNATURES is derived from the header, so it is checked from outside the parser: against ctypes written out by hand
+    for entry points that cover every type and shape the header uses, and against an arity counted by this file's own regex."""
     from homan_amd import lib
+    VP, I, F, SZ, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
+    sil_bwd = [VP, VP, I, I, I, I, F, F, I, VP, VP, VP, VP, VP, VP, VP, VP, VP]
+    want = {
+        "hm_sil_fwd": (I, [VP, VP, I, VP, I, I, I, I, F, F, F, VP, VP, VP, VP, VP, VP, VP, VP, I, VP, VP, VP, I, I, VP, VP]),
+        "hm_sil_bwd_phase_clips": (I, sil_bwd + [I, VP, I, I, I, VP]),
+        "hm_pair_terms_fwd_clips": (I, [VP, VP, VP, I, I, I, VP, VP, VP, F, F, VP, VP, VP, VP, VP, VP,
+                                        VP, F, VP, VP, VP, VP, VP, L, VP, VP, VP, VP, VP, VP, VP, VP, VP,
+                                        VP, VP, VP, VP, VP, VP, VP, VP, I, I, VP]),
+        "hm_lincomb4": (I, [VP, F, VP, F, VP, F, VP, F, L, VP, VP]),
+        "hm_priors_fwd": (I, [VP, L, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+        "hm_sil_workspace_bytes": (SZ, [I, I, I, I]),
+        "hm_sil_parts": (VP, [VP, I, I, I, I]),
+        "hm_sil_fwd_multi": (I, [VP, I, I, VP]),
+        "hm_reduce_workspace_bytes": (SZ, []),
+    }
+    assert len(want["hm_pair_terms_fwd_clips"][1]) == 45
+    for name, sig in want.items():
+        assert lib._SIGNATURES[name] == sig, name
     text = open(os.path.join(ROOT, "include", "homan_amd.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for name, (res, args) in lib._SIGNATURES.items():
@@ -41,23 +82,47 @@ def test_ctypes_arity_matches_header():
         assert n == len(args), (name, n, len(args))
 
 
-def test_sil_render_struct_matches_header_and_library():
-    """HmSilRender (hm_sil_fwd_multi): the ctypes Structure has the header's fields in the header's order and the size the
-    library was built with (hm_sil_render_bytes: no GPU needed)."""
+@pytest.mark.parametrize("proto", [
+    "int hm_x(double x, hipStream_t stream);", "int hm_x(unsigned n);", "int hm_x(const char* name);", "int hm_x(int);",
+    "int hm_x();", "void hm_x(int n);", "double hm_x(int n);", "int hm_x(int n), hm_y(int n);", "int hm_x(int (*cb)(int));",
+    "int hm_x(int n); int hm_x(float n);", "struct Other { int a; };", "int other(int n);",
+    "typedef struct HmSilRender { float* a, b; } HmSilRender;", "typedef struct HmSilRender { short a; } HmSilRender;"])
+def test_header_parser_refuses_what_it_does_not_know(proto):
+    """A type outside the parser's closed table, or a statement that is no hm_* prototype, raises: nothing becomes an int."""
     from homan_amd import lib
-    text = open(os.path.join(ROOT, "include", "homan_amd.h")).read()
-    body = re.search(r"typedef struct HmSilRender \{(.*?)\} HmSilRender;", text, flags=re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        kind = "p" if "*" in decl else ("f" if decl.startswith("float") else "i")
-        names = re.sub(r"^(const\s+)?(float|int|void)\s*\**", "", decl)
-        fields += [(n.strip().lstrip("*").strip(), kind) for n in names.split(",")]
-    want = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float}
-    assert [(n, want[k]) for n, k in fields] == list(lib.SilRender._fields_)
+    good = "int hm_a(const float* const* p, long n, hipStream_t stream); size_t hm_b(void);"
+    sigs, fields = lib.parse_header(good)
+    assert sigs == {"hm_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]), "hm_b": (ctypes.c_size_t, [])}
+    with pytest.raises(lib.HomanAmdError):
+        lib.parse_header(good + "\n" + proto)
+
+
+def test_sil_render_struct_matches_header_and_library():
+    """HmSilRender (hm_sil_fwd_multi): the ctypes Structure has the header's fields in the header's order - pinned here by hand,
+    names and kinds - and the size the library was built with (hm_sil_render_bytes: no GPU needed)."""
+    from homan_amd import lib
+    fields = ([(n, ctypes.c_void_p) for n in ("verts", "faces", "K", "keep", "ref", "pooled", "work_order", "pooled_depth",
+                                              "rigid_rot6d", "rigid_trans", "rigid_scale", "cam_verts_out", "workspace")]
+              + [(n, ctypes.c_int) for n in ("faces_bstride", "B", "V", "F", "S", "mask_shared", "rigid_abs",
+                                             "persistent_outputs", "clip_len")]
+              + [(n, ctypes.c_float) for n in ("orig_size", "znear", "zfar")])
+    assert list(lib.SilRender._fields_) == fields
     assert lib.lib().hm_sil_render_bytes() == ctypes.sizeof(lib.SilRender)
+
+
+def test_kernel_sources_take_the_abi_from_the_public_header():
+    """The compiler holds every exported definition to include/homan_amd.h: hm_common.h, which every unit includes, includes
+    it, the build puts it on the include path, and no file under csrc/ keeps a copy of the codes or of the struct."""
+    from homan_amd import build
+    common = open(os.path.join(build.CSRC, "hm_common.h")).read()
+    assert re.search(r'^#include "homan_amd\.h"', common, flags=re.M)
+    assert os.path.samefile(build.HEADER, os.path.join(ROOT, "include", "homan_amd.h"))
+    for name in sorted(os.listdir(build.CSRC)):
+        src = open(os.path.join(build.CSRC, name)).read()
+        assert not re.search(r"#\s*define\s+HM_(OK|ERR_\w+)\b", src), name
+        assert not re.search(r"struct\s+HmSilRender\s*\{", src), name
+        if name.endswith(".hip"):
+            assert re.search(r'^#include "(hm_common|raster_ws|pair_bodies)\.h"', src, flags=re.M), name
 
 
 def test_no_cpu_fallback_in_product():

@@ -44,7 +44,10 @@ Two boundaries are kept:
   = `(1,)`), `get_verts_object()`, `get_verts_hand(detach_scale=False)`.  `homan_amd.optimize_hand_object` has the
   reference signature and return triple.  Extensions are keyword-only (`mano_model`, `rend_size`, `mode`).
 * **C ABI (`include/homan_amd.h`, `libhoman_amd.so`).**  Plain pointers + sizes + `hipStream_t`, caller-owned buffers,
-  error codes, no torch types.  The Python layer binds it with `ctypes` (`homan_amd/lib.py`); torch supplies device
+  error codes, no torch types.  The header is the one place that spells the ABI: it is compiled into every unit of
+  `csrc/` (through `hm_common.h`), so a definition that drifts from its declaration stops the build, and the `ctypes` table
+  of the Python layer (`homan_amd/lib.py`) is generated from its text when the module loads, refusing any type it does not
+  know.  A new entry point is added in two places, declaration and definition.  torch supplies device
   memory, streams, the autograd tape and `torch.distributed` only.  The silhouette backward leaves its per-(face, corner)
   gradients as doubles (`hm_sil_parts`) and takes, like `hm_rigid_bwd_sil*`, the grid of the order-independent sums
   (`sum_log2q`, section 2).  There is **no CPU fallback**: `lib.lib()` raises if
