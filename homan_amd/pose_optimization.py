@@ -254,13 +254,50 @@ def _graph_loop(model, lr, num_iterations):
     return losses_out, best_rot.clone(), best_trans.clone()
 
 
+def _edge_sum_log2q(lw_chamfer, size, kernel_size, power, base=-24):
+    """Grid 2^q of the backward's order-independent sums (include/homan_amd.h) for a fused loop WITH the edge-chamfer term.
+    The masked L2 alone has |d loss / d alpha| <= 2 per sample and runs on 2^`base` (PoseOptimizer.__init__: per-frame sums up
+    to ~1e7 against an exact range of 2^(53 + base) = 5e8).  The chamfer term adds up to lw * k^2 * max edt per sample - every
+    one of the k^2 windows around a sample may name it, and edt < (2 size^2)^power -, so the grid is coarsened by that ratio,
+    rounded up to a power of two: the same headroom as without the term.  (0.5, 256, 7, 0.25) -> -16: exact up to 1.4e11
+    against a largest single pseudo-gradient term lw * 49 * max edt / eps = 4.7e5; resolution 1.5e-5.)"""
+    largest = 2.0 + abs(float(lw_chamfer)) * kernel_size ** 2 * (2.0 * size * size) ** float(power)
+    return max(-60, min(-1, base + math.ceil(math.log2(largest / 2.0))))
+
+
+class _EdgeTermBuffers:
+    """What the edge-chamfer step of `_FusedPoseLoop` owns beyond the loop's buffers: the un-pooled coverage and its gradient
+    image (n, 2S, 2S), the distance transform of the target's edge band, the per-candidate terms {mask + chamfer, IoU, mask,
+    unweighted chamfer sum} and the number of band samples (read by nobody inside the loop)."""
+
+    def __init__(self, model, ref):
+        sctx, dev = model._sil_ctx, ref.device
+        n, stride = sctx.B, 2 * sctx.S
+        self.ref, self.size, self.stride = ref, int(model.image_size), stride
+        self.kernel_size, self.power = int(model._kernel_size), float(model._power)
+        self.alpha, self.grad = torch.zeros(n, stride, stride, device=dev), torch.zeros(n, stride, stride, device=dev)
+        self.edt, self.terms = torch.zeros(stride, stride, device=dev), torch.zeros(n, 4, device=dev)
+        self.band_samples = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.workspace = torch.zeros(_lib.lib().hm_pose_edge_workspace_bytes(n, stride), dtype=torch.uint8, device=dev)
+        self.sum_log2q = _edge_sum_log2q(model.lw_chamfer, self.size, self.kernel_size, self.power, sctx.sum_log2q)
+
+    def refresh(self):
+        """the distance transform of the mask that lies in `ref` now (hm_edge_edt, on the current stream)"""
+        _lib.check(_lib.lib().hm_edge_edt(_lib.ptr(self.ref), self.size, self.stride, self.kernel_size, self.power,
+                                          _lib.ptr(self.edt), _lib.ptr(self.band_samples), _lib.stream()), "hm_edge_edt")
+
+
 class _FusedPoseLoop:
     """The step of reference pose_optimization.py:330-357 as a fixed sequence of C-ABI launches, no autograd tape, captured
     once in a hipGraph and replayed: rigid transform of the n candidates, off-screen penalty (value + vertex gradients in
     one launch, hm_offscreen_fwd), no-anti-aliasing raster with the masked L2 + IoU fused per sample, edge sweeps, pose
     gradients with the silhouette gather inside (hm_rigid_bwd_sil), the fused multi-tensor Adam - what the eager loop spends
     on torch's element-wise kernels (a third of its step) is gone.  The chamfer term is multiplied by its weight 0 at the
-    reference's only call site and is not evaluated (PoseOptimizer.forward does the same).  Best-ever bookkeeping as in
+    reference's only call site and is then not evaluated (PoseOptimizer.forward does the same).  With `lw_chamfer != 0` the
+    rasteriser writes the un-pooled coverage, hm_pose_edge_terms (csrc/poseedge.hip) forms the masked L2, the IoU, the
+    max-pool-edge x distance-transform sum and the per-sample gradient of their weighted total in one pass, and the edge
+    sweeps take that gradient image (hm_sil_bwd mode 3); the distance transform of the target's edge band is built on the
+    device (hm_edge_edt), at construction and by every `restart()`.  Best-ever bookkeeping as in
     `_graph_loop`: the pose is copied AFTER the optimiser step that followed the evaluation (:348-353), strict `<`.
 
     The loop is BOUND to one PoseOptimizer: the graph reads its `rotations` / `translations` / `_keep1` / `_ref1` / `K` where
@@ -271,7 +308,6 @@ class _FusedPoseLoop:
         record {minimum, candidate, NaN flag, that candidate's pose} in `self.log` (log_steps, 16) and the fitter applies the
         best-ever rule over all groups afterwards (hm_pose_keep_best_log)."""
         from .jointopt import HmAdam
-        assert model.lw_chamfer == 0, "the fused loop covers the reference's configuration (lw_chamfer = 0)"
         self.model, self.lr = model, lr
         L, P, ck = _lib.lib(), _lib.ptr, _lib.check
         sctx, dev = model._sil_ctx, model.rotations.device
@@ -297,6 +333,35 @@ class _FusedPoseLoop:
         self.log_steps = int(log_steps)
         self.log = log = f(self.log_steps, 16) if self.log_steps > 0 else None
         self._keepalive = (verts, g_off, off, pooled, frame, ones, rws, tp, tw)
+        self.edge = edge = _EdgeTermBuffers(model, self.ref) if model.lw_chamfer != 0 else None
+
+        def edge_step():
+            """the step with the edge-chamfer term: same chain, the loss and its per-sample gradient from hm_pose_edge_terms"""
+            st = _lib.stream()
+            ck(L.hm_rigid_fwd(P(model.vertices), P(model.rotations), P(model.translations), P(model._one), 0, n, V, None, P(verts),
+                              st), "hm_rigid_fwd")
+            ck(L.hm_offscreen_fwd(P(verts), P(K_one), n, V, NMR_FAR, 100000.0, P(off), P(g_off), st), "hm_offscreen_fwd")
+            ck(L.hm_sil_fwd(P(verts), P(sctx.faces), 0, P(K_all), n, V, F, S, 1.0, ops.NMR_NEAR, ops.NMR_FAR, None, None, None,
+                            P(pooled), None, P(sctx.work_order), None, P(edge.alpha), 0, None, None, None, 0, 0, P(sctx.workspace),
+                            st), "hm_sil_fwd")
+            ck(L.hm_pose_edge_terms(P(edge.alpha), P(keep), P(ref), P(edge.edt), n, edge.size, 2 * S, edge.kernel_size,
+                                    float(model.lw_chamfer), P(edge.terms), P(edge.grad), P(edge.workspace), st),
+               "hm_pose_edge_terms")
+            ck(L.hm_sil_bwd(P(verts), P(K_all), n, V, F, S, 1.0, eps, 3, None, P(edge.grad), None, P(sctx.adj_off),
+                            P(sctx.adj_items), P(sctx.face_order), None, None, P(sctx.workspace), edge.sum_log2q, st), "hm_sil_bwd")
+            ck(L.hm_rigid_bwd_sil(P(model.vertices), P(model.rotations), P(model._one), 0, tp, tw, tn,
+                                  L.hm_sil_parts(P(sctx.workspace), n, V, F, S), P(sctx.adj_off), P(sctx.adj_items), P(verts),
+                                  P(K_all), 1.0, F, n, V, P(model.rotations.grad), P(model.translations.grad), None, P(rws),
+                                  edge.sum_log2q, st),
+               "hm_rigid_bwd_sil")
+            opt.step(zero_grad=False)
+            # (mask + chamfer) + offscreen, the order of sum(loss_dict.values()): terms[:, 0] holds the first sum
+            if log is not None:
+                ck(L.hm_pose_keep_best_log(P(edge.terms), 4, P(off), n, P(model.rotations), P(model.translations), P(opt.step_t),
+                                           self.log_steps, P(log), P(losses_out), st), "hm_pose_keep_best_log")
+            else:
+                ck(L.hm_pose_keep_best(P(edge.terms), 4, P(off), n, P(model.rotations), P(model.translations), P(best_loss),
+                                       P(best_rot), P(best_trans), P(losses_out), st), "hm_pose_keep_best")
 
         def step():
             st = _lib.stream()
@@ -324,8 +389,10 @@ class _FusedPoseLoop:
                 ck(L.hm_pose_keep_best(P(frame), 2, P(off), n, P(model.rotations), P(model.translations), P(best_loss), P(best_rot),
                                        P(best_trans), P(losses_out), st), "hm_pose_keep_best")
 
-        self._step = step
+        self._step = step if edge is None else edge_step
         self.graph = None
+        if edge is not None:
+            edge.refresh()
 
     def restart(self):
         """a new fit in the bound model's tensors: derived inputs refreshed, optimiser and best-ever state as new"""
@@ -342,6 +409,8 @@ class _FusedPoseLoop:
             p.grad.zero_()
         self.best_loss.fill_(float("inf"))
         sctx.invalidate_outputs()
+        if self.edge is not None:
+            self.edge.refresh()           # (the new mask's distance transform, on the stream: no host round trip)
 
     def run(self, num_iterations):
         """`num_iterations` steps.  The first two steps of a loop's life run un-captured (lazy initialisation of the library)
@@ -422,8 +491,9 @@ class PoseFitter:
     all candidates, strict `<` - is applied over the groups' records after the last step: the same champion, the same poses and
     losses as one loop over all candidates, bit for bit (tests/test_poseinit.py)."""
 
-    def __init__(self, vertices, faces, num_initializations, size, lr):
+    def __init__(self, vertices, faces, num_initializations, size, lr, lw_chamfer=0, kernel_size=7, power=0.25):
         n = num_initializations
+        self.term_kw = dict(lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)      # (the edge-chamfer term, :145-147)
         # (same-box bench.py --pose-init N, pose-steps/s with 1 / 2 / 3 / 4 groups: N = 128: 312 k / 354 k / 371 k; 250: 410 k / 420 k /
         #  467 k; 500: 476 k / 533 k / 565 k / 517 k; 2000: 502 k / 574 k / 585 k)
         parts = int(os.environ.get("HOMAN_POSE_PARTS", "0")) or (3 if n >= 96 else 2 if n >= 48 else 1)
@@ -434,7 +504,7 @@ class PoseFitter:
             rot0 = matrix_to_rot6d(torch.eye(3)[None].repeat(hi - lo, 1, 1))
             shell = PoseOptimizer(ref_image=np.zeros((size, size), np.float32), vertices=vertices, faces=faces, rotation_init=rot0,
                                   translation_init=torch.tensor([[[0.0, 0.0, 1.0]]]), num_initializations=hi - lo,
-                                  K=torch.tensor([[[1.0, 0, 0.5], [0, 1.0, 0.5], [0, 0, 1]]]))
+                                  K=torch.tensor([[[1.0, 0, 0.5], [0, 1.0, 0.5], [0, 0, 1]]]), **self.term_kw)
             self.shells.append(shell)
         self.lr = lr
         self.shell = self.shells[0]                # (one group: the loop's own best-ever state, as before)
@@ -467,9 +537,10 @@ class PoseFitter:
             self._result_shell = PoseOptimizer(ref_image=np.zeros((self.size, self.size), np.float32), vertices=sh0.vertices[0],
                                                faces=sh0.faces[0], rotation_init=matrix_to_rot6d(torch.eye(3)[None].repeat(self.n, 1, 1)),
                                                translation_init=torch.tensor([[[0.0, 0.0, 1.0]]]), num_initializations=self.n,
-                                               K=torch.tensor([[[1.0, 0, 0.5], [0, 1.0, 0.5], [0, 0, 1]]]))
+                                               K=torch.tensor([[[1.0, 0, 0.5], [0, 1.0, 0.5], [0, 0, 1]]]), **self.term_kw)
         result = PoseOptimizer(ref_image=mask, vertices=None, faces=None, rotation_init=rotation_init,
-                               translation_init=translation_init, num_initializations=self.n, K=K, _shared=self._result_shell)
+                               translation_init=translation_init, num_initializations=self.n, K=K, _shared=self._result_shell,
+                               **self.term_kw)
         loops = self._loops_for(num_iterations)
         with torch.no_grad():
             for (lo, hi), sh in zip(zip(self.cuts[:-1], self.cuts[1:]), self.shells):
@@ -525,7 +596,7 @@ class PoseFitter:
     def _fit_one(self, mask, rotation_init, translation_init, K, num_iterations):
         sh = self.shell
         result = PoseOptimizer(ref_image=mask, vertices=None, faces=None, rotation_init=rotation_init,
-                               translation_init=translation_init, num_initializations=self.n, K=K, _shared=sh)
+                               translation_init=translation_init, num_initializations=self.n, K=K, _shared=sh, **self.term_kw)
         with torch.no_grad():
             sh._keep1.copy_(result._keep1)
             sh._ref1.copy_(result._ref1)
@@ -568,17 +639,18 @@ def _digest(t):
     return hash((tuple(t.shape), str(t.dtype), t.detach().cpu().contiguous().numpy().tobytes()))
 
 
-def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None):
+def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None, lw_chamfer=0, kernel_size=7, power=0.25):
     import os
     if os.environ.get("HOMAN_POSE_FITTER", "1") == "0":
         return None
     mesh_key = mesh_key or (_digest(vertices), _digest(faces))
-    key = (*mesh_key, tuple(vertices.shape), tuple(faces.shape), int(n), int(size), float(lr))
+    key = (*mesh_key, tuple(vertices.shape), tuple(faces.shape), int(n), int(size), float(lr), float(lw_chamfer),
+           int(kernel_size), float(power))
     fitter = _FITTERS.get(key)
     if fitter is None:
         while len(_FITTERS) >= _fitters_max():
             _FITTERS.popitem(last=False)              # least recently used
-        fitter = _FITTERS[key] = PoseFitter(vertices, faces, n, size, lr)
+        fitter = _FITTERS[key] = PoseFitter(vertices, faces, n, size, lr, lw_chamfer, kernel_size, power)
     else:
         _FITTERS.move_to_end(key)
     return fitter
@@ -586,10 +658,13 @@ def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None):
 
 def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=None, num_iterations=50,
                       num_initializations=2000, lr=1e-2, image=None, debug=False, viz_folder="tmp", viz_step=10,
-                      sort_best=True, rotations_init=None, viz=False, rend_size=constants.REND_SIZE, mode="auto"):
+                      sort_best=True, rotations_init=None, viz=False, rend_size=constants.REND_SIZE, mode="auto",
+                      lw_chamfer=0, kernel_size=7, power=0.25):
     """reference homan/pose_optimization.py:219-383 (debug plots not provided: `debug` / `viz` / `image` are accepted
     and ignored).  Returns the PoseOptimizer whose `rotations` / `translations` hold the best-ever pose first, then the
     poses sorted by final loss.
+    lw_chamfer / kernel_size / power: weight and shape of the one-way edge-chamfer term (PoseOptimizer's keywords of the same
+    names, :145-147; the reference's call site leaves the weight at 0), in every mode.
     mode="auto" (default) = "fused": the step as a fixed C-ABI launch sequence without the autograd tape, in a hipGraph
     (`_FusedPoseLoop`), run by a resident `PoseFitter` kept per (mesh, candidates, mask size, lr) - HOMAN_POSE_FITTER=0
     builds everything anew per call;
@@ -615,14 +690,16 @@ def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=No
         raise ValueError(f"mode {mode} not in [auto|fused|eager|graph]")
     fitter = None
     if mode == "fused" and num_iterations > 0 and np.asarray(mask).shape[0] % 2 == 0:
-        fitter = _resident_fitter(vertices, faces, num_initializations, int(np.asarray(mask).shape[0]), lr, mesh_key)
+        fitter = _resident_fitter(vertices, faces, num_initializations, int(np.asarray(mask).shape[0]), lr, mesh_key,
+                                  lw_chamfer, kernel_size, power)
     if fitter is not None:
         model, final_losses, champion_rot, champion_trans = fitter.fit(mask, matrix_to_rot6d(rotations_init), translations_init,
                                                                        camintr_roi, num_iterations)
         _install_ranked_poses(model, final_losses, champion_rot, champion_trans, sort_best)
         return model
     model = PoseOptimizer(ref_image=mask, vertices=vertices, faces=faces, rotation_init=matrix_to_rot6d(rotations_init),
-                          translation_init=translations_init, num_initializations=num_initializations, K=camintr_roi)
+                          translation_init=translations_init, num_initializations=num_initializations, K=camintr_roi,
+                          lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)
     if mode == "fused" and num_iterations > 0:
         final_losses, champion_rot, champion_trans = _fused_loop(model, lr, num_iterations)
     elif mode == "graph" and num_iterations > 0:
@@ -679,7 +756,7 @@ def rot6d_to_matrix(rot_6d):
 
 def find_optimal_poses(image_size, faces=None, vertices=None, annotations=None, images=None, Ks=None, num_iterations=50,
                        num_initializations=2000, viz_path="tmp.png", debug=False, rend_size=constants.REND_SIZE,
-                       mode="auto"):
+                       mode="auto", lw_chamfer=0, kernel_size=7, power=0.25):
     """reference homan/pose_optimization.py:386-488 - the entry point of fit_vid_dataset.py:285-296.  One
     `find_optimal_pose` fit per frame, every frame started from the previous frame's `num_initializations` rotations
     (`sort_best=False` keeps the candidates aligned across frames); the motion kept is the candidate with the highest mean
@@ -701,7 +778,8 @@ def find_optimal_poses(image_size, faces=None, vertices=None, annotations=None, 
         fit = find_optimal_pose(vertices=mesh_v, faces=mesh_f, image=pictures[t], mask=ann["target_crop_mask"],
                                 bbox=ann["bbox"], square_bbox=ann["square_bbox"], image_size=image_size, K=Ks[t],
                                 num_iterations=num_iterations, num_initializations=num_initializations, debug=debug,
-                                sort_best=False, rotations_init=seed_rotations, rend_size=rend_size, mode=mode)
+                                sort_best=False, rotations_init=seed_rotations, rend_size=rend_size, mode=mode,
+                                lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)
         with torch.no_grad():
             cand_iou.append(fit()[1].detach())
             cand_verts.append(fit.apply_transformation().detach())

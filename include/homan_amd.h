@@ -91,6 +91,30 @@ int hm_pose_keep_best(const float* sums, int stride, const float* extra, int n, 
  * counter of hm_adam_step, read after the step that followed the evaluation. */
 int hm_pose_keep_best_log(const float* sums, int stride, const float* extra, int n, const float* rot6d, const float* trans,
                           const int* step, int max_steps, float* log, float* losses_out, hipStream_t stream);
+/* One-way edge-chamfer term of the pose initialisation, reference homan/pose_optimization.py:74-88,136-150 (csrc/poseedge.hip).
+ * hm_edge_edt: the distance-transform image of a target mask.  ref: (size, size) samples, 0 / 1, `stride` floats per row
+ *   (stride >= size; size <= 2048).  Edge band = maxpool_k(ref) - ref > 0 with the window clipped to `size`; d2 = the exact
+ *   squared Euclidean distance to the nearest band sample (integer arithmetic); edt[y * stride + x] = float(pow((double) d2,
+ *   power)) - power 0.25, the reference's default, as sqrt(sqrt(d2)): its `distance_transform_edt(...) ** (power * 2)` bit
+ *   for bit.  band_count (one device int) receives the number of band samples; a mask without any (empty or full target) has
+ *   no defined transform (scipy returns distances to a corner there): edt is then all zero and the term vanishes.  Samples
+ *   outside (size, size) are not written.  kernel_size odd, <= 7, else HM_ERR_UNSUPPORTED. */
+int hm_edge_edt(const float* ref, int size, int stride, int kernel_size, float power, float* edt, int* band_count,
+                hipStream_t stream);
+/* hm_pose_edge_terms: one pass over the un-pooled coverage alpha (N, stride, stride) of hm_sil_fwd (`alpha_full`) with the
+ *   shared keep / ref / edt images (`stride` floats per row, the top-left (size, size) block counts), image = keep * alpha:
+ *   terms (N,4) = {mask + lw_chamfer * chamfer, IoU, mask, chamfer} with mask = sum (image - ref)^2, IoU = batch_mask_iou
+ *   (+ 1e-6; both as hm_sil_reduce's frame_out on binary masks), chamfer = sum (maxpool_k(image) - image) * edt; terms[4 i]
+ *   is what the loop minimises before the off-screen penalty joins (hm_pose_keep_best with stride 4);
+ *   grad (N, stride, stride) = d terms[4 i] / d alpha_i = 2 keep (image - ref) + lw_chamfer keep (sum_{q: argmax(q) = p} edt[q]
+ *   - edt[p]), zero outside (size, size): the input of hm_sil_bwd mode 3.  argmax(q) is torch's max-pool rule: the first
+ *   sample, in row-major order of the window clipped to the image, that holds the window's maximum (an all-zero window
+ *   names its top-left sample).  Fixed summation order, no floating-point atomics: two calls agree bit for bit.
+ *   kernel_size odd, 3..7, else HM_ERR_UNSUPPORTED; N <= 65535.  workspace: hm_pose_edge_workspace_bytes(N, stride) bytes,
+ *   zero-filled once (self-resetting tickets). */
+size_t hm_pose_edge_workspace_bytes(int N, int stride);
+int hm_pose_edge_terms(const float* alpha, const float* keep, const float* ref, const float* edt, int N, int size, int stride,
+                       int kernel_size, float lw_chamfer, float* terms, float* grad, void* workspace, hipStream_t stream);
 /* out = s[0] * in ;  out = s0[0]*a + s1[0]*b   (backward of the losses whose unit gradient is produced forward) */
 int hm_scale_by(const float* in, const float* s, long n, float* out, hipStream_t stream);
 int hm_scale2_by(const float* a, const float* s0, const float* b, const float* s1, long n, float* out,
