@@ -498,4 +498,21 @@ int hm_collision_read_grid(const int* faces, int V, int F, int B, int which, int
                        which == 0 ? w.vn0 : w.vn1, faces, V, F, B, w.masks + (size_t)which * B * SDF_N * SDF_N, phi);
     return hm_launch_status();
 }
+
+// Debug view of the LAZY path (what k_sdf_need listed and k_sdf_dist evaluated, where hm_collision_read_grid recomputes every
+// inside voxel by brute force): need-mask (B,32,32) words, bit i <-> voxel x index i; list length (B); phi (B,32,32,32) as the
+// workspace holds it - defined only where the need bit is set, elsewhere whatever an earlier call left.  Device-to-device copies.
+int hm_collision_read_needed(int B, int which, int V0, int V1, int F0, int F1, void* need_mask, int* need_len, float* phi,
+                             void* workspace, hipStream_t stream)
+{
+    HM_CHECK_ARG(need_mask && need_len && phi && workspace && B > 0 && (which == 0 || which == 1));
+    CollWs w;
+    coll_layout(workspace, B, V0, V1, F0, F1, &w);
+    const size_t rows = (size_t)SDF_N * SDF_N, grid = rows * SDF_N;
+    if (hipMemcpyAsync(need_mask, w.needm + (size_t)which * B * rows, B * rows * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(need_len, w.need_cnt + (size_t)which * B, (size_t)B * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(phi, w.phi + (size_t)which * B * grid, B * grid * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        return HM_ERR_LAUNCH;
+    return HM_OK;
+}
 }  // extern "C"

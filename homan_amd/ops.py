@@ -759,6 +759,19 @@ class CollisionContext:
                    "hm_collision_read_grid")
         return phi
 
+    def needed(self, which):
+        """The lazy evaluation of the last forward for mesh `which` (debug): need-mask (B,32,32) int32 words (bit i of word
+        [z][y] <-> voxel (z,y,i) is inside and touched by a sample), list length (B) int32, and phi (B,32,32,32) as the
+        workspace holds it - defined only where the need bit is set."""
+        dev = self.ws.device
+        mask = torch.empty(self.B, 32, 32, dtype=torch.int32, device=dev)
+        cnt = torch.empty(self.B, dtype=torch.int32, device=dev)
+        phi = torch.empty(self.B, 32, 32, 32, device=dev)
+        _lib.check(_lib.lib().hm_collision_read_needed(self.B, which, self.V0, self.V1, self.f0.shape[0], self.f1.shape[0],
+                                                       _lib.ptr(mask), _lib.ptr(cnt), _lib.ptr(phi), _lib.ptr(self.ws),
+                                                       _lib.stream()), "hm_collision_read_needed")
+        return mask, cnt, phi
+
 
 class _CollisionLoss(torch.autograd.Function):
     """reference homan/lossutils.py:43-64 (sdf branch) -> interactions/scenesdf.py:77-148."""

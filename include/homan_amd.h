@@ -381,6 +381,11 @@ int hm_collision_dist_values(const float* verts0, int V0, const float* verts1, i
 /* clamp(SDF,0) on the full 32^3 grid of mesh `which`, from the workspace of the last hm_collision_fwd */
 int hm_collision_read_grid(const int* faces, int V, int F, int B, int which, int V0, int V1, int F0, int F1, float* phi,
                            void* workspace, hipStream_t stream);
+/* what the LAZY evaluation of the last hm_collision_fwd left for mesh `which` (read_grid recomputes every inside voxel): need_mask
+ * (B,32,32) 32-bit words, bit i of word [z][y] <-> voxel (z,y,i) was touched by a sample and is inside; need_len (B) = length
+ * of the voxel list (= set bits); phi (B,32,32,32) distances, defined only where the need bit is set.  Read-only. */
+int hm_collision_read_needed(int B, int which, int V0, int V1, int F0, int F1, void* need_mask, int* need_len, float* phi,
+                             void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------ optimiser step + logging
  * reference homan/jointopt.py:138-151,192 (torch.optim.Adam, three groups) and :184-189 (loss_evolution).

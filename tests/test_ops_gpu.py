@@ -219,7 +219,10 @@ def test_collision_vs_oracle(obj, mano_model):
         assert ((got > 0) == (ref > 0)).all(), f"inside masks differ for mesh {which}"
         _close(got, ref, rtol=1e-5, msg=f"phi {which}")
         # ... bit for bit, in fact: a min over the triangles of ONE point-triangle routine (csrc/sdf.hip <-> oracle/csrc/sdf.c);
-        # the written-out collision term of the free-running parity runs relies on it (oracle/handchain.py)
+        # the written-out collision term of the free-running parity runs relies on it (oracle/handchain.py).  `cctx.grid` is the
+        # brute-force debug kernel k_sdf_grid on the sign pass's masks: this equality covers the sign pass and the point-triangle
+        # routine, NOT the lazy evaluation the loss itself uses (k_sdf_need + k_sdf_dist: nearest-vertex seed, pruning by the
+        # triangles' boxes) - that one is held to this grid voxel by voxel in tests/test_pairterms_edges_gpu.py
         assert torch.equal(got, ref.float().clamp(min=0)), f"phi {which}: {(got - ref).abs().max().item()}"
     _close(lh, lo, rtol=1e-4, msg="collision loss")
     _close(ah.grad, a.grad, rtol=1e-3, atol_frac=1e-3, msg="collision grad hand")

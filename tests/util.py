@@ -310,3 +310,283 @@ def ordinal_scene3(B=6, S=64, seed=1):
     a2[1::2] = 0.0
     m2 = (rng.random(shp) < 0.3).astype(np.uint8)
     return dict(d=sc["d"] + [d2], a=sc["a"] + [a2], m=sc["m"] + [m2])
+
+
+# ===================================================================== pair terms: references and shared scenes
+# (tests/test_pairterms_refs.py checks the references against the CPU oracle and measures the float32 floors;
+#  tests/test_pairterms_edges_gpu.py holds the kernels of csrc/pair_bodies.h, contact.hip and sdf.hip against them)
+NN_SHAPES = [(1, 1), (1, 64), (1, 4097), (64, 3), (64, 65), (64, 4096), (127, 63), (127, 257), (128, 64), (128, 4097), (129, 1),
+             (129, 65), (129, 257), (778, 3), (778, 4096), (778, 4097)]          # (Vh, Vo): every value of either axis of the grid
+
+
+def nn_bruteforce32(vh, vo):
+    """Nearest object vertex of every hand vertex in float32, d2 = ((ox-hx)^2 + (oy-hy)^2) + (oz-hz)^2 with every operation
+    rounded (numpy does not contract), first argmin.  vh (B,Vh,3), vo (B,Vo,3) float32 numpy -> idx (B,Vh) int64, d2 (B,Vh)
+    float32, metric = max_b sqrt32(min_i d2) float32."""
+    vh, vo = np.asarray(vh, np.float32), np.asarray(vo, np.float32)
+    d = [vo[:, None, :, c] - vh[:, :, None, c] for c in range(3)]
+    d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+    assert d2.dtype == np.float32
+    idx = d2.argmin(2)
+    best = np.take_along_axis(d2, idx[..., None], 2)[..., 0]
+    return idx, best, np.sqrt(best.min(1)).max()
+
+
+def nn_clouds(B, Vh, Vo, seed=0):
+    """random float32 clouds, the object's next to the hand's (some hand vertices inside it)"""
+    rng = np.random.default_rng([seed, B, Vh, Vo])
+    vh = (rng.normal(size=(B, Vh, 3)) * 0.04 + [0.02, 0.0, 0.6]).astype(np.float32)
+    vo = (rng.normal(size=(B, Vo, 3)) * 0.05 + [0.0, 0.0, 0.62]).astype(np.float32)
+    return vh, vo
+
+
+def nn_tie_clouds(B, Vh, Vo, seed=0):
+    """Coordinates on multiples of 1/4 in [0, 1] (a lattice of 125 points, every squared distance exact in float32): an object
+    of several hundred vertices holds each point many times over and every hand vertex has its minimum at many indices."""
+    rng = np.random.default_rng([seed, B, Vh, Vo, 7])
+    vh = (rng.integers(0, 5, size=(B, Vh, 3)) / 4.0 + 1.0 / 64.0).astype(np.float32)      # (off the object's lattice by 1/64)
+    vo = (rng.integers(0, 5, size=(B, Vo, 3)) / 4.0).astype(np.float32)
+    return vh, vo
+
+
+def nn_tie_spread(d2, waves=4):
+    """How the equal minima of exact squared distances d2 (B,Vh,Vo) fall on the full search's layout (csrc/pair_bodies.h: wave q
+    scans the contiguous share [q s, (q+1) s), s = ceil(Vo / waves), 64 at a time) -> (hand vertices whose minimum lies in more
+    than one wave's share, hand vertices with it in more than one 64-group of a single share)"""
+    Vo = d2.shape[2]
+    share = -(-Vo // waves)
+    at_min = d2 == d2.min(2, keepdims=True)
+    j = np.arange(Vo)
+    wave, group = j // share, (j % share) // 64
+    in_wave = np.stack([(at_min & (wave == q)).any(2) for q in range(waves)])
+    two_groups = np.zeros(d2.shape[:2], bool)
+    for q in range(waves):
+        two_groups |= np.stack([(at_min & (wave == q) & (group == g)).any(2) for g in range(group.max() + 1)]).sum(0) >= 2
+    return int((in_wave.sum(0) >= 2).sum()), int(two_groups.sum())
+
+
+# ---- contact
+CONTACT_THRESH = 0.02
+CONTACT_VO = (1, 64, 4096, 4097, 9000)       # one range | one range, full | two ranges with a tail of one | three ranges
+CONTACT_VH = (1, 255, 257, 778)
+CONTACT_B = (1, 3)
+
+
+def contact_scene(B, Vh, Vo, kind="random", seed=0, zeros=0):
+    """-> vh (B,Vh,3), vo (B,Vo,3) float32, nn (B,Vh) int32.  The picks are GIVEN (no search, no near-tie ambiguity) and the hand
+    vertex sits at distance thresh * 10^U(-4, log10 20) from its pick: a / thresh log-uniform over [1e-4, 20], the linear end and
+    full saturation.  kind: "random" picks | "same" every vertex picks one object vertex | "last_range" picks >= 4096 * (ranges - 1).
+    zeros: that many hand vertices per frame coincide with their pick (a == 0)."""
+    rng = np.random.default_rng([seed, B, Vh, Vo, len(kind)])
+    vo = (rng.normal(size=(B, Vo, 3)) * 0.05 + [0.0, 0.0, 0.6]).astype(np.float32)
+    if kind == "random":
+        nn = rng.integers(0, Vo, size=(B, Vh))
+    elif kind == "same":
+        nn = np.full((B, Vh), min(17, Vo - 1))
+    elif kind == "last_range":
+        nn = rng.integers(4096 * ((Vo - 1) // 4096), Vo, size=(B, Vh))
+    else:
+        raise ValueError(kind)
+    u = rng.normal(size=(B, Vh, 3))
+    u /= np.linalg.norm(u, axis=-1, keepdims=True)
+    r = CONTACT_THRESH * 10.0 ** rng.uniform(-4.0, np.log10(20.0), size=(B, Vh, 1))
+    if Vh >= 2:
+        r[:, 0], r[:, 1] = CONTACT_THRESH * 1e-4, CONTACT_THRESH * 20.0         # both ends are there
+    picked = np.take_along_axis(vo, nn[..., None].repeat(3, -1), 1)
+    vh = (picked.astype(np.float64) + r * u).astype(np.float32)
+    for z in range(zeros):
+        vh[:, (3 + 5 * z) % Vh] = picked[:, (3 + 5 * z) % Vh]
+    return vh, vo, nn.astype(np.int32)
+
+
+def contact_ref(vh, vo, nn, thresh=CONTACT_THRESH, dtype=torch.float64, clip_len=None):
+    """mean_{b,i} thresh tanh(|o_nn - h| / thresh) (reference contactloss.py as executed, csrc/contact.hip) with torch autograd
+    for both gradients -> (loss (C,), g_hand, g_obj).  A pair at distance 0 has value 0 and subgradient 0 (the kernels'
+    convention; autograd through the norm alone gives NaN there).  clip_len: one mean per clip of that many frames."""
+    h = torch.as_tensor(vh).to(dtype).requires_grad_(True)
+    o = torch.as_tensor(vo).to(dtype).requires_grad_(True)
+    idx = torch.as_tensor(nn).long()
+    d = torch.gather(o, 1, idx[..., None].expand(-1, -1, 3)) - h
+    a2 = (d * d).sum(-1)
+    live = a2 > 0
+    a = torch.sqrt(torch.where(live, a2, torch.ones_like(a2)))
+    val = torch.where(live, thresh * torch.tanh(a / thresh), torch.zeros_like(a))
+    B, Vh = val.shape
+    loss = val.reshape(-1, clip_len or B, Vh).mean((1, 2))
+    loss.sum().backward()
+    return loss.detach(), h.grad, o.grad
+
+
+# ---- SDF interpenetration
+def tetrahedron():
+    v = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], np.float32) * 0.0125
+    return v, np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]], np.int32)          # outward
+
+
+def octahedron():
+    v = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float32)
+    f = np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]], np.int32)      # outward
+    return v, f
+
+
+def _posed(v, B, shift, seed, turn=0.35, wobble=0.004):
+    """(V,3) -> (B,V,3) float32: turned by a frame-dependent angle about x and y, moved by `shift` plus a small seeded wobble"""
+    from homan_amd import synth
+    rng = np.random.default_rng([seed, B, len(v)])
+    out = []
+    for b in range(B):
+        R = synth._rot_x(turn * (b + 1) * 0.7) @ synth._rot_y(turn * (b + 1))
+        out.append(v.astype(np.float64) @ R.T + np.asarray(shift) + rng.normal(size=3) * wobble)
+    return np.stack(out).astype(np.float32)
+
+
+def sdf_scenes(mano):
+    """name -> (verts0 (B,V0,3), faces0, verts1 (B,V1,3), faces1), float32 / int32 numpy: the closed meshes of the pair-term edge
+    tests (each mesh reaches into the other unless said otherwise), and the two scenes of test_ops_gpu.test_collision_vs_oracle."""
+    from homan_amd import synth
+    hv, hf = mano["v_template"].astype(np.float32), mano["closed_faces"].astype(np.int32)
+    tv, tf = tetrahedron()
+    b1v, b1f = synth.box_mesh(1, 1, 1)
+    bav, baf = synth.box_mesh(4, 4, 6)
+    bbv, bbf = synth.box_mesh(1, 1, 32)
+    btv, btf = synth.bottle_mesh()
+    assert (len(tv), len(tf), len(b1v), len(b1f)) == (4, 4, 8, 12) and len(baf) == 256 and len(bbf) == 260
+    ctr = np.array([0.02, -0.01, 0.6])
+    sc = {}
+    tet, box = _posed(tv, 2, ctr + [0.004, 0.003, 0.01], 1), _posed(b1v, 2, ctr, 2)
+    sc["tet_in_box"] = (tet, tf, box, b1f)
+    sc["box_around_tet"] = (box, b1f, tet, tf)
+    sc["F256_vs_F260"] = (_posed(bav, 2, ctr, 3), baf, _posed(bbv * [0.5, 0.5, 1.0], 2, ctr + [0.006, -0.004, 0.02], 4, turn=0.2), bbf)
+    hand = _posed(hv, 2, ctr - [0.02, 0.0, 0.0], 5, turn=0.1)
+    sc["hand_vs_box8"] = (hand, hf, _posed(b1v * 1.6, 2, ctr + [0.012, 0.0, 0.0], 6), b1f)
+    sc["bottle_vs_hand"] = (_posed(btv, 2, ctr + [0.05, 0.0, 0.01], 7, turn=0.05), btf, hand, hf)
+    # tests/test_ops_gpu.py::test_collision_vs_oracle, written out
+    g = torch.Generator().manual_seed(4)
+    B = 3
+    vh = torch.from_numpy(hv)[None].repeat(B, 1, 1) + torch.randn(B, 1, 3, generator=g) * 0.01 + torch.tensor([0.0, 0.0, 0.55])
+    vo = torch.from_numpy(btv)[None].repeat(B, 1, 1) + torch.tensor([0.02, 0.0, 0.56]) + torch.randn(B, 1, 3, generator=g) * 0.01
+    vh = vh + torch.tensor([0.03, 0.0, 0.0])
+    sc["ops_bottle"] = (vh.numpy(), hf, vo.numpy(), btf)
+    cv, cf = synth.box_mesh()
+    vc = torch.from_numpy(cv)[None].repeat(B, 1, 1) * 1.5 + vh.mean(1, keepdim=True) + torch.tensor([0.01, 0.0, 0.0])
+    sc["ops_cube"] = (vh.numpy(), hf, vc.numpy(), cf)
+    return {k: tuple(np.ascontiguousarray(x) for x in v) for k, v in sc.items()}
+
+
+SDF_SCENE_NAMES = ("tet_in_box", "box_around_tet", "F256_vs_F260", "hand_vs_box8", "bottle_vs_hand", "ops_bottle", "ops_cube")
+OCTA_SCALE, OCTA_OFFSET, OCTA_INSIDE = 0.125, (0.5, -0.25, 2.0), 5440
+
+
+def octahedron_scene():
+    """Unit octahedron at a power-of-two scale and offset (scale_factor 0: its normalised box is the unit octahedron exactly, the
+    voxel centres (odd / 32) sit ON the projected edges |y| + |z| = 1) and a half-size copy inside it.  -> scene tuple, B = 1."""
+    v, f = octahedron()
+    big = (v * OCTA_SCALE + np.asarray(OCTA_OFFSET, np.float32))[None].astype(np.float32)
+    small = (v * (OCTA_SCALE / 2) + np.asarray(OCTA_OFFSET, np.float32))[None].astype(np.float32)
+    return big, f, small, f
+
+
+def octahedron_exact():
+    """-> inside (32,32,32) bool [z][y][x], phi (32,32,32) float64 = (1 - |x| - |y| - |z|) / sqrt 3 inside, 0 outside"""
+    c = -1.0 + (np.arange(32) + 0.5) / 16.0
+    s = np.abs(c)[:, None, None] + np.abs(c)[None, :, None] + np.abs(c)[None, None, :]
+    assert not (s == 1).any()
+    return s < 1, np.where(s < 1, (1 - s) / np.sqrt(3.0), 0.0)
+
+
+def frames_scene():
+    """B = 4, boxes of 44 and 26 vertices about one unit across: frame 0 overlapping, 1 disjoint, 2 the second wholly inside the
+    first, 3 the second 2^20 away (its coordinates stay exact there: multiples of 1/8)."""
+    from homan_amd import synth
+    av, af = synth.box_mesh(3, 3, 2, scale=2.0)
+    bv, bf = synth.box_mesh(2, 2, 2, scale=2.0)
+    a = _posed(av, 4, [0.1, -0.2, 3.0], 11, turn=0.1, wobble=0.02)
+    b = _posed(bv, 4, [0.1, -0.2, 3.0], 12, turn=0.15, wobble=0.02)
+    b[0] += np.float32([0.3, 0.2, 0.25])
+    b[1] += np.float32([3.0, 0.0, 0.0])
+    b[2] = (0.3 * (b[2] - b[2].mean(0)) + a[2].mean(0)).astype(np.float32)
+    cube = np.sign(bv) * np.float32(0.5) * (bv != 0)                   # 26 vertices on {-0.5, 0, 0.5}^3
+    b[3] = (cube + np.float32([2.0 ** 20, 0.0, 3.0])).astype(np.float32)
+    return a, af, b, bf
+
+
+SHELL_IX = (-1.0, -0.5, -1e-3, 0.0, 30.999, 31.0, 31.5, 32.0)
+
+
+def shell_scene():
+    """Owner (slot 0): a cube of half-side 1/4 about (0.5, -0.25, 2.0); with scale_factor 0 its normalised box fills the grid
+    exactly (every voxel inside, centre and scale powers of two).  Sampled (slot 1): a tetrahedron inside it, plus 24 loose
+    vertices (no face uses them) at grid index SHELL_IX on each axis in turn, the other two indices at 10.25 and 17.5 - in the
+    zero-padded border shell, on it, and beyond it.  The integer indices are exact in float32.  -> scene tuple (B = 1), and
+    the (24, 3) grid indices of the loose vertices."""
+    from homan_amd import synth
+    bv, bf = synth.box_mesh(1, 1, 1)
+    c, s = np.asarray(OCTA_OFFSET, np.float64), 0.25
+    owner = (np.sign(bv) * s + c).astype(np.float32)
+    tv, tf = tetrahedron()
+    ix = []
+    for axis in range(3):
+        for x in SHELL_IX:
+            p = [10.25, 17.5, 10.25]
+            p[(axis + 1) % 3], p[axis] = 17.5, x
+            ix.append(p)
+    ix = np.asarray(ix, np.float64)
+    loose = c + s * ((2.0 * ix + 1.0) / 32.0 - 1.0)
+    sampled = np.concatenate([tv * 4.0 + c + [0.03, -0.02, 0.05], loose]).astype(np.float32)
+    return (owner[None], bf, sampled[None], tf), ix
+
+
+def sdf_need_ref(verts_owner, verts_sampled, inside, scale_factor):
+    """The voxels the lazy evaluation must list, per frame: the 8 trilinear corners of every sample point, inside the grid and
+    inside the owner's mesh - from the float32 index arithmetic of sdf_sample_setup (csrc/sdf.hip), operation by operation.
+    verts_* (B,V,3) float32, inside (B,32,32,32) bool [z][y][x] -> (B,32,32,32) bool."""
+    f32 = np.float32
+    vo, vs = np.asarray(verts_owner, f32), np.asarray(verts_sampled, f32)
+    lo, hi = vo.min(1), vo.max(1)
+    ctr = (lo + hi) / f32(2.0)
+    sc = ((hi - lo) * ((f32(1.0) + f32(scale_factor)) * f32(0.5))).max(1)
+    need = np.zeros(inside.shape, bool)
+    for b in range(len(vs)):
+        l = (vs[b] - ctr[b]) / sc[b]
+        ix = ((l + f32(1.0)) * f32(32.0) - f32(1.0)) / f32(2.0)
+        assert ix.dtype == f32
+        i0 = np.floor(np.minimum(np.maximum(ix, f32(-4.0)), f32(36.0))).astype(np.int64)
+        for corner in range(8):
+            x, y, z = i0[:, 0] + (corner & 1), i0[:, 1] + ((corner >> 1) & 1), i0[:, 2] + (corner >> 2)
+            ok = (x >= 0) & (x < 32) & (y >= 0) & (y < 32) & (z >= 0) & (z < 32)
+            need[b, z[ok], y[ok], x[ok]] = True
+    return need & inside
+
+
+def sdf_scene_ref(phis, verts, scale_factor=0.2, dtype=torch.float64):
+    """SDFSceneLoss (reference scenesdf.py:77-148) on GIVEN grids: phis = the oracle's float32 clamp(SDF, 0) of both meshes
+    (B,32,32,32); box centre and scale, normalisation, trilinear sampling (grid_sample, zeros padding, align_corners=False) in
+    `dtype`; loss = sum over both ordered pairs; gradients by autograd to the sampled vertices only (boxes and grids are
+    constants, as in the reference).  -> loss (0-d), [g0, g1], {(k, l): (B,V_l) sample x owner scale}."""
+    v = [torch.as_tensor(x).to(dtype).requires_grad_(True) for x in verts]
+    loss, dist = torch.zeros((), dtype=dtype), {}
+    for k, l in ((0, 1), (1, 0)):
+        with torch.no_grad():
+            lo, hi = v[k].min(1)[0], v[k].max(1)[0]
+            ctr = ((lo + hi) / 2)[:, None]
+            sc = ((hi - lo) * ((1 + scale_factor) * 0.5)).max(-1)[0]
+        local = (v[l] - ctr) / sc.view(-1, 1, 1)
+        d = torch.nn.functional.grid_sample(torch.as_tensor(phis[k]).to(dtype)[:, None], local.view(local.shape[0], -1, 1, 1, 3),
+                                            mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0, :, 0, 0]
+        dist[(k, l)] = (d * sc[:, None]).detach()
+        loss = loss + d.sum()
+    if loss.requires_grad:
+        loss.backward()
+    return loss.detach(), [x.grad if x.grad is not None else torch.zeros_like(x) for x in v], dist
+
+
+def oracle_sdf(scene, scale_factor=0.2):
+    """the CPU oracle (float32) on a scene tuple -> loss, [g0, g1], meta (sdfs, dist_values)"""
+    from oracle import model as om
+    v0, f0, v1, f1 = scene
+    a, b = torch.from_numpy(v0).clone().requires_grad_(True), torch.from_numpy(v1).clone().requires_grad_(True)
+    loss, meta = om.sdf_scene_loss([torch.from_numpy(f0), torch.from_numpy(f1)], [a, b], scale_factor=scale_factor)
+    if loss.requires_grad:
+        loss.backward()
+    g = [x.grad if x.grad is not None else torch.zeros_like(x) for x in (a, b)]
+    return loss.detach(), g, meta
