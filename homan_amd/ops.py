@@ -845,3 +845,37 @@ def align_stats(gt_hand, pred_hand, frames, pred_centroid_from_gt=True):
                                          _lib.ptr(aff_gt), _lib.ptr(aff_pred), _lib.ptr(hand_mean), _lib.stream()),
                "hm_align_stats")
     return aff_gt, aff_pred, hand_mean
+
+
+def keyframe_interp(key_vals, key_frames, frame_nb, gather=None, signs=(1.0, 1.0, 1.0), out_dtype=torch.float32):
+    """Key-frame values (K,N,3) at the sorted host frame numbers `key_frames` -> every frame of the sequence, (frame_nb, M, 3)
+    fp32 or fp64 (no grad; csrc/seqinterp.hip): the blend of reference homan/eval/ho3devalutils.py:53-96, then per-coordinate
+    `signs` (+-1) and the row `gather` (M host indices into N, repeats allowed).  The library checks the host arrays before it
+    enqueues anything; a refused call raises ValueError."""
+    if out_dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"out_dtype must be float32 or float64, got {out_dtype}")
+    key_vals = _f32(key_vals.detach())
+    if key_vals.dim() != 3 or key_vals.shape[2] != 3:
+        raise ValueError(f"key_vals: expected (K, N, 3), got {tuple(key_vals.shape)}")
+    K, N = key_vals.shape[0], key_vals.shape[1]
+    kf = np.ascontiguousarray(np.asarray(key_frames).reshape(-1), dtype=np.int32)
+    if kf.shape[0] != K:
+        raise ValueError(f"{kf.shape[0]} key frames for {K} key values")
+    ga = None if gather is None else np.ascontiguousarray(np.asarray(gather).reshape(-1), dtype=np.int32)
+    M = N if ga is None else ga.shape[0]
+    sg = np.ascontiguousarray(np.asarray(signs, dtype=np.float32).reshape(-1))
+    if sg.shape[0] != 3:
+        raise ValueError("signs: three values, each +1 or -1")
+    dev = key_vals.device
+    kf_dev = torch.empty(max(K, 1), dtype=torch.int32, device=dev)
+    ga_dev = None if ga is None else torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    out = torch.empty(max(int(frame_nb), 0), M, 3, dtype=out_dtype, device=dev)
+    rc = _lib.lib().hm_keyframe_interp(_lib.ptr(key_vals), kf.ctypes.data, K, N, int(frame_nb),
+                                       None if ga is None else ga.ctypes.data, M, sg.ctypes.data,
+                                       int(out_dtype == torch.float64), _lib.ptr(kf_dev), _lib.ptr(ga_dev), _lib.ptr(out),
+                                       _lib.stream())
+    if rc == -1:
+        raise ValueError(f"hm_keyframe_interp refused its arguments: key frames {kf.tolist()[:8]}... must start at 0, increase "
+                         f"strictly and end at or before frame_nb = {frame_nb}; gather must index [0, {N}); signs must be +-1")
+    _lib.check(rc, "hm_keyframe_interp")
+    return out

@@ -335,6 +335,23 @@ int hm_cloud_metrics(const float* x, const float* y, int B, int N, int M, const 
 int hm_align_stats(const float* gt_hand, const float* pred_hand, int B, int hands, int V, int pred_centroid_from_gt,
                    float* aff_gt, float* aff_pred, double* hand_mean, hipStream_t stream);
 
+/* ------------------------------------------------------------------ sequence evaluation: key-frame interpolation
+ * reference homan/eval/ho3devalutils.py:53-96 (interpolate_res) followed by the per-frame `.dot(camextr)[unorder_idxs]
+ * .astype(np.float32)` of evalho3drecons.py:126-127,154-158, for one key of one sequence in one launch (csrc/seqinterp.hip).
+ *   key_vals (K,N,3) fp32 device; key_frames: HOST int[K], strictly increasing, key_frames[0] == 0, key_frames[K-1] <= frame_nb;
+ *   gather: HOST int[M] rows of N (repeats allowed) or NULL (then M == N); signs: HOST float[3], each +1 or -1 (the diagonal
+ *   of camextr); out (frame_nb, M, 3) device, fp32 (out_f64 == 0) or fp64.
+ * Frame f with k_j <= f < k_{j+1} receives s + (e - s) * w: the difference in fp32, w = (double)(f - k_j) * (1.0 / (double)(k_{j+1}
+ * - k_j)) (np.linspace's weights), product and sum in double, each operation rounded once; frames at or after the last key
+ * receive that key's value (K == 1: every frame; the reference raises a NameError there).  The sign is applied to the double,
+ * then the fp32 output rounds once; the fp64 output with signs (1,1,1) is what interpolate_res returns.
+ * The host arrays are checked first (HM_ERR_BAD_ARG: order, first and last key, gather range, signs) and nothing is enqueued
+ * when they fail.  Then they are copied, on `stream`, into the caller's device buffers key_frames_dev (K ints) and gather_dev
+ * (M ints; NULL without gather), which the kernel reads: the host arrays are read during the call only (pageable memory), so
+ * the call is stream-ordered but not capturable in a hipGraph. */
+int hm_keyframe_interp(const float* key_vals, const int* key_frames, int K, int N, int frame_nb, const int* gather, int M,
+                       const float* signs, int out_f64, int* key_frames_dev, int* gather_dev, void* out, hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
