@@ -41,7 +41,7 @@ class ClipBatch(nn.Module):
         self.models, self.C = models, len(models)
         self.clip_len = m0.translations_object.shape[0]
         self.B = self.C * self.clip_len
-        for k in ("optimize_mano", "optimize_object_scale", "hand_proj_mode", "image_size", "hand_nb"):
+        for k in ("optimize_mano", "optimize_object_scale", "hand_proj_mode", "image_size", "hand_nb", "sil_mode"):
             vals = {getattr(m, k) for m in models}
             assert len(vals) == 1, f"clips of one batch must agree on {k}: {vals}"
             setattr(self, k, getattr(m0, k))

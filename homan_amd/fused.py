@@ -85,6 +85,10 @@ class FusedStepper:
         for one in (model.models if isinstance(model, ClipBatch) else model if isinstance(model, (list, tuple)) else [model]):
             if len(one.hand_sides) not in (1, 2):
                 raise NotImplementedError("one or two hands per frame")
+            if getattr(one, "sil_mode", "nmr") != "nmr":
+                # the launch sequence below renders with the hard rasteriser whatever the model says: refuse, so that
+                # mode="auto" and ClipFitter fall back to HOMan.forward + autograd in a hipGraph, which honours the mode
+                raise NotImplementedError("sil_mode='soft': the fused loop renders hard silhouettes only (mode='graph' or 'eager')")
         m = self.model = model if isinstance(model, ClipBatch) else ClipBatch(model if isinstance(model, (list, tuple))
                                                                              else [model])
         if len({tuple(one.hand_sides) for one in m.models}) != 1:

@@ -59,7 +59,12 @@ class HOMan(nn.Module):
                  optimize_mano_beta=True, inter_type="centroid", image_size=640,
                  # homan_amd extensions (keyword-only use)
                  mano_model=None, mano_root="extra_data/mano", rend_size=constants.REND_SIZE, sync_metrics=True,
-                 ordinal_depth=False):
+                 ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4):
+        # (host-side checks of the options first: no device is touched before they pass)
+        if sil_mode not in ("nmr", "soft"):
+            raise ValueError(f"sil_mode {sil_mode} not in [nmr|soft]")
+        if not float(sil_sigma) > 0 or float(sil_sigma) == float("inf"):
+            raise ValueError(f"sil_sigma {sil_sigma} must be a positive number (NDC^2)")
         super().__init__()
         if not torch.cuda.is_available():
             raise RuntimeError("homan_amd.HOMan needs an MI355X (ROCm) device; there is no CPU path")
@@ -156,6 +161,12 @@ class HOMan(nn.Module):
         self.mano_model = ManoModel(mano_root, pca_comps=16, mano_model=mano_model, device=dev)
         self.sync_metrics = sync_metrics
         self.reduce_ws = ops.ReduceWorkspace(dev)
+        # sil_mode="soft" (a homan_amd extra, NOT the reference's image formation: DESIGN.md section 7): the object silhouette term
+        # renders with the Soft Rasterizer op, whose gradient is a true derivative, all three coordinates included.  Its blur
+        # `sil_sigma` (NDC^2) is a plain device tensor - no buffer, no Parameter: the state_dict keys stay the reference's - that
+        # the kernels read when they run, so `model.sil_sigma.mul_(0.5)` between steps anneals it, captured graphs included.
+        self.sil_mode = sil_mode
+        self.sil_sigma = torch.full((1,), float(sil_sigma), dtype=torch.float32, device=dev)
         num_verts_object = self.verts_object_og.shape[1]
         self.losses = Losses(renderer=None, ref_mask_object=self.ref_mask_object,
                              keep_mask_object=self.keep_mask_object, ref_mask_hand=self.ref_mask_hand,
@@ -163,7 +174,8 @@ class HOMan(nn.Module):
                              camintr_rois_object=self.camintr_rois_object, camintr_rois_hand=self.camintr_rois_hand,
                              camintr=self.camintr, class_name=class_name, hand_nb=self.hand_nb, inter_type=inter_type,
                              faces_object=self.faces_object, num_verts_object=num_verts_object, rend_size=rend_size,
-                             reduce_ws=self.reduce_ws, sync_metrics=sync_metrics)
+                             reduce_ws=self.reduce_ws, sync_metrics=sync_metrics, sil_mode=sil_mode,
+                             sil_sigma=self.sil_sigma)
         closed = np.asarray(self.mano_model.closed_faces)
         if self.hand_nb == 1:
             self.collision_ctx = ops.CollisionContext(closed, self.faces_object[0], batch, 778, num_verts_object, dev)

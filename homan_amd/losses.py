@@ -8,7 +8,7 @@ class Losses:
     def __init__(self, renderer, ref_mask_object, ref_verts2d_hand, keep_mask_object, ref_mask_hand, keep_mask_hand,
                  camintr_rois_object, camintr_rois_hand, camintr, class_name, inter_type="min", hand_nb=1,
                  faces_object=None, num_verts_object=None, rend_size=constants.REND_SIZE, reduce_ws=None,
-                 sync_metrics=True):
+                 sync_metrics=True, sil_mode="nmr", sil_sigma=None):
         if inter_type not in ("centroid", "min"):
             raise ValueError(f"inter_type {inter_type} not in [centroid|min]")
         self.inter_type = inter_type
@@ -25,7 +25,17 @@ class Losses:
         self.sync_metrics = sync_metrics
         dev = ref_mask_object.device
         B = ref_mask_object.shape[0]
-        self.sil_ctx = ops.SilhouetteContext(faces_object, num_verts_object, B, rend_size, dev)
+        # sil_mode "soft": the object silhouette through the Soft Rasterizer op (a non-parity extra, ops.soft_silhouette_render)
+        # instead of the reference's hard rasteriser; sil_sigma = its blur, a 1-element device tensor read when the kernels run
+        if sil_mode not in ("nmr", "soft"):
+            raise ValueError(f"sil_mode {sil_mode} not in [nmr|soft]")
+        self.sil_mode, self.sil_sigma = sil_mode, sil_sigma
+        if sil_mode == "soft":
+            if sil_sigma is None:
+                raise ValueError("sil_mode='soft' needs sil_sigma (1-element float32 device tensor)")
+            self.sil_ctx = ops.SoftSilhouetteContext(faces_object, num_verts_object, B, rend_size, dev)
+        else:
+            self.sil_ctx = ops.SilhouetteContext(faces_object, num_verts_object, B, rend_size, dev)
         self.keep_sum = keep_mask_object.sum().reshape(1)
         self.last_silhouettes = None
 
@@ -39,6 +49,16 @@ class Losses:
 
     def compute_sil_loss_object(self, verts, faces=None):
         """reference losses.py:183-197."""
+        if self.sil_mode == "soft":
+            # the expression of :189-196 on the soft image (the render is the hot path; these are a few image-sized torch ops)
+            sil = ops.soft_silhouette_render(verts, self.camintr_rois_object, self.sil_ctx, self.sil_sigma)
+            image = self.keep_mask_object * sil
+            loss = (torch.sum((image - self.ref_mask_object) ** 2) / self.keep_sum / len(verts)).reshape(1)
+            with torch.no_grad():       # libyana batch_mask_iou (:195), mean over the frames
+                union = (image + self.ref_mask_object).clamp(0, 1)
+                iou = ((image * self.ref_mask_object).sum((1, 2)) / (union.sum((1, 2)) + 1e-6)).mean()
+            self.last_silhouettes = sil.detach()
+            return {"loss_sil_obj": loss}, {"iou_object": self._metric(iou)}
         loss, iou, sil = ops.silhouette_loss(verts, self.camintr_rois_object, self.keep_mask_object,
                                              self.ref_mask_object, self.keep_sum, self.sil_ctx)
         self.last_silhouettes = sil

@@ -317,6 +317,64 @@ def silhouette_render(verts, K, sctx, orig_size=1.0):
     return _SilhouetteRender.apply(verts, K, sctx, orig_size)
 
 
+class SoftSilhouetteContext:
+    """Per-call-site state of the soft silhouette op (csrc/softsil.hip; a non-parity extra, see include/homan_amd.h): topology,
+    CSR adjacency and the workspace, allocated once.  Any image size from 1 to 4096: the 32-pixel grid of the hard path does not
+    apply, so nothing is padded and K is used as given."""
+
+    def __init__(self, faces, num_verts, batch, size, device):
+        assert faces.dim() == 3 and faces.shape[0] == batch
+        f0 = faces[0].detach().cpu().numpy()
+        if batch > 1:
+            assert bool((faces == faces[:1]).all()), "per-frame topologies must be identical"
+        self.B, self.V, self.F, self.S = batch, num_verts, f0.shape[0], int(size)
+        self.size = self.S
+        self.faces = faces[0].to(device=device, dtype=torch.int32).contiguous()
+        off, items = build_adjacency(f0, num_verts)
+        self.adj_off, self.adj_items = off.to(device), items.to(device)
+        nbytes = _lib.lib().hm_softsil_workspace_bytes(self.B, self.V, self.F, self.S)
+        if nbytes == 0:
+            raise _lib.HomanAmdError(f"soft silhouettes: unsupported shape B={self.B} V={self.V} F={self.F} S={self.S}")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    def invalidate_outputs(self):
+        """(the hard context's hook for new masks in resident buffers, HOMan.load_clip: every soft render writes every pixel)"""
+
+
+class _SoftSilhouetteRender(torch.autograd.Function):
+    """Soft Rasterizer silhouettes (Liu et al. 2019) with their true gradient; stands beside reference homan/losses.py:187."""
+
+    @staticmethod
+    def forward(ctx, verts, K, sctx, sigma, orig_size):
+        verts, K = _f32(verts), _f32(K)
+        assert sigma.dtype == torch.float32 and sigma.numel() == 1 and sigma.device == verts.device
+        alpha = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
+        _lib.check(_lib.lib().hm_softsil_fwd(
+            _lib.ptr(verts), _lib.ptr(sctx.faces), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(orig_size),
+            NMR_NEAR, NMR_FAR, _lib.ptr(sigma), _lib.ptr(alpha), _lib.ptr(sctx.workspace), _lib.stream()), "hm_softsil_fwd")
+        ctx.save_for_backward(verts, K, alpha)
+        ctx.sctx, ctx.sigma, ctx.orig_size = sctx, sigma, orig_size        # (sigma: the live tensor, read again by the backward)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, g_img):
+        verts, K, alpha = ctx.saved_tensors
+        sctx = ctx.sctx
+        g_img = _f32(g_img)
+        grad_verts = torch.empty_like(verts)
+        _lib.check(_lib.lib().hm_softsil_bwd(
+            _lib.ptr(verts), _lib.ptr(sctx.faces), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size),
+            NMR_NEAR, NMR_FAR, _lib.ptr(ctx.sigma), _lib.ptr(alpha), _lib.ptr(g_img), _lib.ptr(sctx.adj_off),
+            _lib.ptr(sctx.adj_items), _lib.ptr(grad_verts), _lib.ptr(sctx.workspace), _lib.stream()), "hm_softsil_bwd")
+        return grad_verts, None, None, None, None
+
+
+def soft_silhouette_render(verts, K, sctx, sigma, orig_size=1.0):
+    """-> (B,S,S) soft coverage.  sigma: 1-element float32 device tensor (NDC^2), read by the kernels when they run - a value
+    changed in place is followed by a captured graph; not differentiable."""
+    return _SoftSilhouetteRender.apply(verts, K, sctx, sigma, orig_size)
+
+
 class _DepthRender(torch.autograd.Function):
     """reference homan/homan.py:391,406: `_, depths, sils = renderer.render(verts, faces, textures, K=)`.
     -> (silhouettes (B,S,S), depths (B,S,S)); only the depth image is differentiable here (the ordinal depth loss uses

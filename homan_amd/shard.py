@@ -20,7 +20,8 @@ def _shape_signature(model):
     return (int(model.translations_object.shape[0]), int(model.verts_object_og.shape[1]), faces.shape[0], hash(faces.tobytes()),
             tuple(model.hand_sides), bool(model.optimize_mano), bool(model.optimize_object_scale), model.hand_proj_mode,
             int(model.image_size), int(model.losses.sil_ctx.size), int(model.mano_pca_pose.shape[1]),
-            bool(model.int_scales_hand.requires_grad), model.losses.inter_type, bool(getattr(model, "ordinal_depth", False)))
+            bool(model.int_scales_hand.requires_grad), model.losses.inter_type, bool(getattr(model, "ordinal_depth", False)),
+            getattr(model, "sil_mode", "nmr"))
 
 
 class ShardStepper:
@@ -32,11 +33,17 @@ class ShardStepper:
 
     shared_scale (BASELINE cfg5): ONE object scale tied across all clips of all ranks.  The steppers compute their clips'
     gradient sums, this class adds them, issues the rank's ONE all-reduce per iteration (and its one broadcast at the start)
-    - so ranks with different numbers of shape groups, or with none, stay in step - and hands the global sum back."""
+    - so ranks with different numbers of shape groups, or with none, stay in step - and hands the global sum back.
+
+    Soft-mode clips (HOMan(sil_mode="soft")) are refused with NotImplementedError: the shard runs on fused steppers, and the
+    fused loop renders hard silhouettes only (ClipFitter and optimize_hand_object(mode="auto") take such clips through the
+    autograd hipGraph instead)."""
 
     def __init__(self, models, loss_weights, lr, max_steps, shared_scale=False, group=None, capture=True):
         from . import dist as hdist
         self.models, self.shared_scale, self.group, self.hdist = list(models), bool(shared_scale), group, hdist
+        if any(getattr(mdl, "sil_mode", "nmr") != "nmr" for mdl in self.models):
+            raise NotImplementedError("ShardStepper: sil_mode='soft' clips are not covered by the fused loop")
         groups = OrderedDict()
         for i, mdl in enumerate(self.models):
             groups.setdefault(_shape_signature(mdl), []).append(i)
@@ -188,13 +195,13 @@ class ClipFitter:
 
     def __init__(self, loss_weights, num_iterations=400, lr=1e-2, clips_per_batch=1, max_resident=4, class_name="default",
                  hand_proj_mode="persp", optimize_mano=True, optimize_mano_beta=True, optimize_object_scale=False,
-                 image_size=640, mano_model=None, rend_size=256, ordinal_depth=False):
+                 image_size=640, mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4):
         self.lw, self.steps, self.lr = dict(loss_weights), int(num_iterations), float(lr)
         self.cpb, self.max_resident = max(1, int(clips_per_batch)), max(1, int(max_resident))
         self.model_kw = dict(class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode, optimize_mano=optimize_mano,
                              optimize_mano_beta=optimize_mano_beta, optimize_object_scale=optimize_object_scale,
                              image_size=image_size, mano_model=mano_model, rend_size=rend_size, sync_metrics=False,
-                             ordinal_depth=ordinal_depth)
+                             ordinal_depth=ordinal_depth, sil_mode=sil_mode, sil_sigma=sil_sigma)
         self.resident = OrderedDict()          # (signature, clips) -> FusedStepper
         self._one_by_one = set()          # shape signatures whose clips the fused loop takes one at a time
         self._graph_only = set()          # ... and those it refuses altogether (ortho, free hand scale): the autograd hipGraph

@@ -284,6 +284,36 @@ int hm_sil_read_parts(const void* workspace, int B, int V, int F, int S, double*
 /* per-face screen boxes (B,F) x 8 bytes {x0|winding<<14, y0, x1, y1} u16 */
 int hm_sil_read_boxes(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream);
 
+/* ------------------------------------------------------------------ soft silhouettes (NON-PARITY extra; csrc/softsil.hip)
+ * Liu, Li, Chen, Li, "Soft Rasterizer: A Differentiable Renderer for Image-based 3D Reasoning", ICCV 2019, silhouette branch:
+ * an image formation of its own that stands BESIDE the hard rasteriser the reference calls at homan/losses.py:187 - the
+ * reference has no counterpart, nothing here is compared against it.  What it buys: a true gradient (the hard path's is NMR's
+ * pseudo-gradient of a piecewise constant image), also along the camera-space z, and a blur radius the caller can anneal.
+ *   verts (B,V,3) camera space, faces (F,3) int32 shared by the frames, K (B,3,3), orig_size: projected exactly as by hm_sil_fwd.
+ *   Pixel (row r, column c) of the (B,S,S) image has its centre at x = (2c + 1 - S) / S, y = (S - 1 - 2r) / S (NDC; what the hard
+ *   rasteriser gives that pixel without anti-aliasing, output flip included).
+ *   A face takes part if its three camera-space z lie strictly inside (znear, zfar), |twice its signed NDC area| >= 1e-10 and its
+ *   indices are inside [0, V); winding plays no role.  Other faces contribute nothing and receive a zero gradient.
+ *   Per pixel p and face j: d2 = squared NDC distance from p to the nearest of the three edge segments, x = +d2 / sigma if p is
+ *   in the closed triangle, else -d2 / sigma; D = sigmoid(x).  An outside pair with d2 >= 16 sigma is dropped exactly (D = 0,
+ *   no gradient; sigmoid(-16) = 1.13e-7).  alpha_p = 1 - prod_j (1 - D_jp), the factors 1 - D formed as sigmoid(-x) and
+ *   multiplied in ascending face index.
+ *   sigma: DEVICE pointer to one float, read by the kernels when they RUN - a captured hipGraph follows a value changed in place
+ *   between replays.  A value that is not a positive finite number renders an empty image (alpha = 0, gradient 0).
+ *   Backward, the true derivative: d alpha_p / d x_jp = (1 - alpha_p) D_jp, d x / d d2 = +-1 / sigma, d2 to the two end points of
+ *   the nearest segment (one of them at a clamped end), then through the projection to all three coordinates of the vertices;
+ *   sigma receives none.  alpha = the forward's output for the same arguments; grad_alpha (B,S,S); adj_off (V+1) / adj_items (3F)
+ *   as for hm_sil_bwd; grad_verts (B,V,3) is overwritten.
+ *   Any S in 1..4096, F >= 1, B >= 1 (else HM_ERR_BAD_ARG, like a NULL pointer: nothing is launched, outputs stay untouched).
+ *   workspace: hm_softsil_workspace_bytes bytes (0 for shapes outside that range), no initialisation needed.  Every sum has a
+ *   fixed order and no result goes through an atomic: two calls on the same inputs return the same bits. */
+size_t hm_softsil_workspace_bytes(int B, int V, int F, int S);
+int hm_softsil_fwd(const float* verts, const int* faces, const float* K, int B, int V, int F, int S, float orig_size,
+                   float znear, float zfar, const float* sigma, float* alpha, void* workspace, hipStream_t stream);
+int hm_softsil_bwd(const float* verts, const int* faces, const float* K, int B, int V, int F, int S, float orig_size,
+                   float znear, float zfar, const float* sigma, const float* alpha, const float* grad_alpha,
+                   const int* adj_off, const int* adj_items, float* grad_verts, void* workspace, hipStream_t stream);
+
 /* ------------------------------------------------------------------ small losses (value + unit gradient in one launch)
  * workspace for all of them: hm_reduce_workspace_bytes(), zero-filled once. */
 size_t hm_reduce_workspace_bytes(void);
