@@ -118,11 +118,6 @@ int hm_log_total_clips(float* vals, const float* weights, int n, const int* step
     hipLaunchKernelGGL(k_log_total, dim3(nclips), dim3(64), 0, stream, vals, weights, n, step, max_steps, log);
     return hm_launch_status();
 }
-int hm_log_total(float* vals, const float* weights, int n, const int* step, int max_steps, float* log,
-                 hipStream_t stream)
-{
-    return hm_log_total_clips(vals, weights, n, step, max_steps, log, 1, stream);
-}
 size_t hm_adam_slot_bytes(void) { return sizeof(AdamSlot); }
 
 int hm_adam_step(const void* slots, int n_tensors, int* step, float beta1, float beta2, float eps, int zero_grad,

@@ -360,15 +360,6 @@ int hm_hand_terms_fwd_clips(const float* verts, const float* camintr, int hand_n
                        ws_counter(workspace), out_stride);
     return hm_launch_status();
 }
-int hm_hand_terms_fwd(const float* verts, const float* camintr, int hand_nb, const float* ref2d, float image_size, int N,
-                      int V, float* unit_v2d, float* out_v2d2, float* unit_smooth, float* out_smooth1, const float* pca,
-                      long npca, const float* s_obj, const float* m_obj, const float* s_hand, const float* m_hand,
-                      float* g_pca, float* g_sobj, float* g_shand, float* out_priors3, void* workspace, hipStream_t stream)
-{
-    return hm_hand_terms_fwd_clips(verts, camintr, hand_nb, ref2d, image_size, N, V, unit_v2d, out_v2d2, unit_smooth,
-                                   out_smooth1, pca, npca, s_obj, m_obj, s_hand, m_hand, g_pca, g_sobj, g_shand,
-                                   out_priors3, workspace, 0, 0, stream);
-}
 // frame_rec: (B,8) floats kept for the backward.
 int hm_inter_fwd_clips(const float* verts_hand, const float* verts_obj, const float* camintr, int B, int Vh, int Vo,
                        float expansion, float zthresh, float* frame_rec, float* out1, void* workspace, int clip_len,

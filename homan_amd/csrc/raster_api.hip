@@ -36,12 +36,6 @@ int& hm_sweep_cap_override()
     static int cap = 0;
     return cap;
 }
-// measurement hook (hm_debug_sil_timing): HIP events recorded on the launch stream right before / after the three heavy
-// kernels of the silhouette chain, so a caller that drives the optimisation loop launch by launch (not from a captured
-// graph) reads the duration each kernel had INSIDE the loop, next to whatever runs on the other streams
-static hipEvent_t g_tev[6];
-static int g_timing = 0;
-#define HM_TIME_MARK(k, stream) do { if (g_timing) (void)hipEventRecord(g_tev[k], stream); } while (0)
 
 extern "C" {
 
@@ -141,9 +135,7 @@ int hm_sil_fwd_phase_clips(const float* verts, const int* faces, int faces_bstri
     RasterFwdArgs a = {B, F, S, znear, zfar, pooled, keep, ref, fused, work_order, pooled_depth, bins, 1, persistent_outputs,
                        alpha_full, mask_shared, fused && (alpha_full || (mask_shared & 2)), tune.raster_reorder != 0,
                        tune.raster_lds_pad};
-    HM_TIME_MARK(0, stream);
     hm_launch_raster_fwd(w, a, stream);
-    HM_TIME_MARK(1, stream);
     if (fused && keep_sum && loss_out) hm_launch_sil_reduce(w, B, S, keep_sum, loss_out, nullptr, clip_len, out_stride, stream);
     return hm_launch_status();
 }
@@ -253,7 +245,7 @@ int hm_sil_reduce(int B, int V, int F, int S, const float* keep_sum, float* loss
 // that suffers most from latency-bound neighbours holding its wave slots); hm_sil_bwd_clips = both
 int hm_sil_bwd_phase_clips(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                            const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-                           const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+                           const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                            int clip_len, float* loss_out, int out_stride, int phases, int sum_log2q, hipStream_t stream)
 {
     HM_CHECK_ARG(!loss_out || ((mode == 1 || mode == 2) && keep_sum));
@@ -268,30 +260,27 @@ int hm_sil_bwd_phase_clips(const float* verts, const float* K, int B, int V, int
     HM_CHECK_ARG(phases >= 1 && phases <= 3);
     if ((phases & 1) && mode != 2 && mode != 4 && mode != 5)      // modes 2 / 4 / 5: the caller guarantees upstream > 0, the forward's planes are the backward's
         hm_launch_bwd_masks(w, mode == 1 ? w.dimg : grad_pooled, mode, upstream, keep_sum, B, S, clip_len, stream);
-    HM_TIME_MARK(2, stream);
     if (phases & 1) hm_launch_lines(w, B, F, S, mode, upstream, keep_sum, clip_len, stream, loss_out, out_stride);
-    HM_TIME_MARK(3, stream);
     if (!(phases & 2)) return hm_launch_status();
     hm_launch_sweep(w, B, F, S, eps, sum_log2q, stream);
-    HM_TIME_MARK(4, stream);
     if (grad_verts) hm_launch_bwd_gather(w, adj_off, adj_items, verts, K, B, V, F, orig_size, grad_ndc, grad_verts, stream);
     return hm_launch_status();
 }
 int hm_sil_bwd_clips(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                      const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-                     const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+                     const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                      int clip_len, float* loss_out, int out_stride, int sum_log2q, hipStream_t stream)
 {
     return hm_sil_bwd_phase_clips(verts, K, B, V, F, S, orig_size, eps, mode, upstream, grad_pooled, keep_sum, adj_off, adj_items,
-                                  face_order, grad_verts, grad_ndc, workspace, clip_len, loss_out, out_stride, 3, sum_log2q, stream);
+                                  grad_verts, grad_ndc, workspace, clip_len, loss_out, out_stride, 3, sum_log2q, stream);
 }
 int hm_sil_bwd(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-               const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+               const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                int sum_log2q, hipStream_t stream)
 {
     return hm_sil_bwd_clips(verts, K, B, V, F, S, orig_size, eps, mode, upstream, grad_pooled, keep_sum, adj_off, adj_items,
-                            face_order, grad_verts, grad_ndc, workspace, 0, nullptr, 0, sum_log2q, stream);
+                            grad_verts, grad_ndc, workspace, 0, nullptr, 0, sum_log2q, stream);
 }
 
 // (B,F,3,2) DOUBLES: d loss / d NDC (x, y) per face corner, as left by the last hm_sil_bwd (exact sums of terms on the
@@ -323,7 +312,7 @@ int hm_shade_rgb(const float* verts, const int* faces, int faces_bstride, const 
 // milliseconds.  Synchronises.
 int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, int B, int V, int F, int S,
                          const float* keep, const float* ref, const float* keep_sum, float* pooled, float* loss_out,
-                         const int* work_order, const int* adj_off, const int* adj_items, const int* face_order,
+                         const int* work_order, const int* adj_off, const int* adj_items,
                          const float* upstream, float* grad_verts, void* workspace, int reps, float* avg_ms,
                          hipStream_t stream)
 {
@@ -332,7 +321,7 @@ int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, i
     int rc = hm_sil_fwd(verts, faces, 0, K, B, V, F, S, 1.0f, 0.1f, 100.0f, keep, ref, keep_sum, pooled, loss_out,
                         work_order, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, workspace, stream);
     if (rc != HM_OK) return rc;
-    rc = hm_sil_bwd(verts, K, B, V, F, S, 1.0f, 1e-3f, 1, upstream, nullptr, keep_sum, adj_off, adj_items, face_order,
+    rc = hm_sil_bwd(verts, K, B, V, F, S, 1.0f, 1e-3f, 1, upstream, nullptr, keep_sum, adj_off, adj_items,
                     grad_verts, nullptr, workspace, 0, stream);
     if (rc != HM_OK) return rc;
     SilWs w = carve(workspace, B, V, F, S);
@@ -368,20 +357,6 @@ int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, i
     return hm_launch_status();
 }
 
-// enable != 0: from now on hm_sil_fwd / hm_sil_bwd record HIP events around k_raster_fwd, k_bwd_lines and k_bwd_sweep on
-// their launch stream (do not enable while a stream capture is in progress); 0: stop and release the events.
-int hm_debug_sil_timing(int enable)
-{
-    if (enable && !g_timing) {
-        for (int k = 0; k < 5; ++k)
-            if (hipEventCreate(&g_tev[k]) != hipSuccess) return HM_ERR_LAUNCH;
-        g_timing = 1;
-    } else if (!enable && g_timing) {
-        g_timing = 0;
-        for (int k = 0; k < 5; ++k) (void)hipEventDestroy(g_tev[k]);
-    }
-    return HM_OK;
-}
 // In-graph timing of the same three kernels: device wall-clock stamps stored by the workgroups themselves (see
 // hm_ts_enabled above), so the numbers come from launches replayed from a captured hipGraph - where ROCm allows no events.
 //   hm_sil_timestamps(ws, B, V, F, S, 1, stream): switch on and arm (two async memsets, no host synchronisation); call
@@ -433,22 +408,6 @@ int hm_sil_timestamps_read(const void* workspace, int B, int V, int F, int S, co
     free(t);
     return HM_OK;
 }
-// durations (ms) of the LAST timed k_raster_fwd, k_bwd_lines, k_bwd_sweep launches -> ms3 (HOST pointer).  Waits for them.
-int hm_debug_sil_timing_read(float* ms3)
-{
-    HM_CHECK_ARG(ms3 && g_timing);
-    if (hipEventSynchronize(g_tev[4]) != hipSuccess) return HM_ERR_LAUNCH;
-    if (hipEventElapsedTime(ms3, g_tev[0], g_tev[1]) != hipSuccess) return HM_ERR_LAUNCH;
-    if (hipEventElapsedTime(ms3 + 1, g_tev[2], g_tev[3]) != hipSuccess) return HM_ERR_LAUNCH;
-    if (hipEventElapsedTime(ms3 + 2, g_tev[3], g_tev[4]) != hipSuccess) return HM_ERR_LAUNCH;
-    return HM_OK;
-}
-int hm_debug_read_partials(const void* workspace, int B, int V, int F, int S, float* out, hipStream_t stream)
-{
-    SilWs w = carve((void*)workspace, B, V, F, S);
-    return hipMemcpyAsync(out, w.partials, (size_t)B * (S / 8) * (S / 8) * 16, hipMemcpyDeviceToDevice, stream) == hipSuccess
-               ? HM_OK : HM_ERR_LAUNCH;
-}
 // test hook: cap > 0 shrinks the unit table and the partial-slot table of the sweep work list to `cap` entries (the
 // workspace keeps its size), so that small inputs exercise the beyond-capacity paths; 0 restores the defaults.
 int hm_debug_sweep_caps(int cap)
@@ -456,11 +415,6 @@ int hm_debug_sweep_caps(int cap)
     const int prev = hm_sweep_cap_override();
     hm_sweep_cap_override() = cap > 0 ? cap : 0;
     return prev;
-}
-int hm_debug_occupancy(int* raster_fwd_blocks, int* sweep_blocks)
-{
-    const int e1 = hm_raster_fwd_occupancy(raster_fwd_blocks), e2 = hm_sweep_occupancy(sweep_blocks);
-    return (e1 == HM_OK && e2 == HM_OK) ? HM_OK : HM_ERR_LAUNCH;
 }
 
 // debug / test access to forward intermediates held in the workspace

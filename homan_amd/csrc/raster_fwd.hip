@@ -696,11 +696,6 @@ void hm_launch_shade_rgb(const SilWs& w, const float* verts, const int* faces, i
                        faces_bstride, textures, B, V, F, S, light_dir[0], light_dir[1], light_dir[2], amb, dirw, background[0],
                        background[1], background[2], rgb);
 }
-int hm_raster_fwd_occupancy(int* blocks_per_cu)
-{
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_raster_fwd, 64 * RASTER_WAVES, 0) == hipSuccess ? HM_OK
-                                                                                                                        : HM_ERR_LAUNCH;
-}
 #ifdef RASTER_TRACE
 extern "C" int hm_debug_raster_trace_filter(int F, int depth)
 {

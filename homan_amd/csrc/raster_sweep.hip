@@ -723,10 +723,6 @@ void hm_launch_bwd_gather(const SilWs& w, const int* adj_off, const int* adj_ite
     hipLaunchKernelGGL(k_bwd_gather, dim3(hm_cdiv((long)B * V, 256)), dim3(256), 0, stream, w.parts, adj_off, adj_items, verts,
                        K, B, V, F, orig_size, grad_ndc, grad_verts);
 }
-int hm_sweep_occupancy(int* blocks_per_cu)
-{
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_bwd_sweep<true>, 256, 0) == hipSuccess ? HM_OK : HM_ERR_LAUNCH;
-}
 #ifdef SWEEP_UNIT_PROFILE
 extern "C" int hm_debug_unit_profile(int* out)              // 65536 x 4 ints, then cleared
 {

@@ -149,5 +149,3 @@ HM_INTERNAL void hm_launch_lines(const SilWs& w, int B, int F, int S, int mode, 
 HM_INTERNAL void hm_launch_sweep(const SilWs& w, int B, int F, int S, float eps, int sum_log2q, hipStream_t stream);
 HM_INTERNAL void hm_launch_bwd_gather(const SilWs& w, const int* adj_off, const int* adj_items, const float* verts, const float* K,
                                       int B, int V, int F, float orig_size, float* grad_ndc, float* grad_verts, hipStream_t stream);
-HM_INTERNAL int hm_sweep_occupancy(int* blocks_per_cu);
-HM_INTERNAL int hm_raster_fwd_occupancy(int* blocks_per_cu);

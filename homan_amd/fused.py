@@ -221,7 +221,6 @@ class FusedStepper:
         sx = m.sil_ctx
         self.sil_K = sx.K_eff(m.camintr_rois_object).contiguous()
         self.sil_keep, self.sil_ref = sx.pad(m.keep_mask_object), sx.pad(m.ref_mask_object)
-        self.sil_eps = sx.eps()
         self.up_sil, self.up_inter = torch.tensor([w["loss_sil_obj"]], device=dev), torch.tensor([w["loss_inter"]], device=dev)
         if self.on["depth"] and h > 1:
             # two hands per frame: the three layers [object, hand 0, hand 1] of reference homan.py:384-419, every unordered pair
@@ -533,8 +532,8 @@ class FusedStepper:
 
     def _aux_block(self, it):
         """the silhouette reduction and the log row on the third stream (clip batches)"""
-        (m, L, P, ck, B, Vo, on, CL, NS, C, sctx, use_aux, log) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.CL, it.NS, it.C, it.sctx, it.use_aux, it.log)
+        (m, L, P, ck, on, CL, NS, C, sctx, use_aux, log) = \
+            (it.m, it.L, it.P, it.ck, it.on, it.CL, it.NS, it.C, it.sctx, it.use_aux, it.log)
         if not use_aux:
             return
         # the silhouette reduction and the log row run on a third stream, off both chains.  (Only this: HIP stream
@@ -546,23 +545,24 @@ class FusedStepper:
             self.aux.wait_event(self.ev_fwd)
             if on["sil"]:
                 self.aux.wait_event(self.ev_ras)
-                ck(L.hm_sil_reduce_clips(B, Vo, sctx.F, sctx.S, P(m.keep_sum), self._slot("loss_sil_obj"), None,
-                                         P(sctx.workspace), CL, NS, self.aux.cuda_stream), "sil_reduce")
+                ck(sctx.reduce(keep_sum=m.keep_sum, loss_out=self._slot("loss_sil_obj"), clip_len=CL, out_stride=NS,
+                               stream=self.aux.cuda_stream), "sil_reduce")
             if log:
                 ck(L.hm_log_total_clips(P(self.vals), P(self.weights), len(self.SLOTS), P(self.opt.step_t),
                                         self.max_steps, P(self.log_buf), C, self.aux.cuda_stream), "log")
 
     def _issue_silhouette_chain(self, it):
         """A, first half: face setup (+ camera-space vertices), fork point, rasteriser, [object depth render], line expansion + sweeps"""
-        (m, L, P, ck, B, Vo, on, CL, NS, main, sa, sctx, use_aux) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.CL, it.NS, it.main, it.sa, it.sctx, it.use_aux)
+        (m, L, ck, on, CL, NS, main, sa, sctx, use_aux) = \
+            (it.m, it.L, it.ck, it.on, it.CL, it.NS, it.main, it.sa, it.sctx, it.use_aux)
         # ---------------- A: silhouettes forward + backward (the critical chain: nothing else rides it; the object's rigid
         # transform is applied inside the face setup, the other losses get the vertices from the side stream)
         if on["sil"]:
-            fwd_args = (P(m.verts_object_og), P(sctx.faces), 0, P(self.sil_K), B, Vo, sctx.F, sctx.S,
-                        1.0, self.ops.NMR_NEAR, self.ops.NMR_FAR, P(self.sil_keep), P(self.sil_ref),
-                        None, P(self.pooled), None, P(sctx.work_order), None, None, 0, P(m.rotations_object),
-                        P(m.translations_object), P(m.int_scales_object), 1, 1, P(sctx.workspace), CL, NS, P(self.vo))
+            # the render: the object's rigid pose applied in the face setup, which also writes the camera-space vertices self.vo
+            render = dict(verts=m.verts_object_og, K=self.sil_K, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
+                          rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object, rigid_scale=m.int_scales_object,
+                          rigid_abs=1, persistent_outputs=1, clip_len=CL, cam_verts_out=self.vo)
+            fwd_args = dict(render, out_stride=NS, stream=sa)
             if self.merge_renders:
                 # with the ordinal depth term: the silhouette render and the OBJECT's depth render (the same mesh and pose at the
                 # full-image camera) as ONE face-setup launch and ONE raster launch (hm_sil_fwd_multi: per render the arguments
@@ -572,51 +572,42 @@ class FusedStepper:
                 # candidates, profiles/r06_raster_trace_depth.txt), which then runs under the silhouette render's two rounds
                 # instead of behind them (cfg2 + depth 4 208 -> 4 303 it/s, same box; results do not depend on the order)
                 arr = _lib.sil_renders([
-                    dict(verts=m.verts_object_og, faces=self.dctx[0].faces, K=m.camintr, B=B, V=Vo, F=self.dctx[0].F,
-                         S=self.dctx[0].S, orig_size=1.0, znear=self.ops.NMR_NEAR, zfar=self.ops.NMR_FAR, pooled=self.d_sil_o,
-                         pooled_depth=self.d_dep_o, work_order=self.dctx[0].work_order, rigid_rot6d=m.rotations_object,
-                         rigid_trans=m.translations_object, rigid_scale=m.int_scales_object, rigid_abs=1,
-                         persistent_outputs=1, workspace=self.dctx[0].workspace, clip_len=CL),
-                    dict(verts=m.verts_object_og, faces=sctx.faces, K=self.sil_K, B=B, V=Vo, F=sctx.F, S=sctx.S, orig_size=1.0,
-                         znear=self.ops.NMR_NEAR, zfar=self.ops.NMR_FAR, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
-                         work_order=sctx.work_order, rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object,
-                         rigid_scale=m.int_scales_object, rigid_abs=1, persistent_outputs=1, workspace=sctx.workspace, clip_len=CL,
-                         cam_verts_out=self.vo)])
+                    self.dctx[0].render_fields(verts=m.verts_object_og, K=m.camintr, pooled=self.d_sil_o, pooled_depth=self.d_dep_o,
+                                               rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object,
+                                               rigid_scale=m.int_scales_object, rigid_abs=1, persistent_outputs=1, clip_len=CL),
+                    sctx.render_fields(**render)])
                 ck(L.hm_sil_fwd_multi(arr, 2, 1, sa), "sil_fwd_multi(setup)")
                 self.ev_sil.record(main)
                 ck(L.hm_sil_fwd_multi(arr, 2, 2, sa), "sil_fwd_multi(raster)")
                 self.ev_dep.record(main)
             elif self.side_own_vo:
-                ck(L.hm_sil_fwd_clips(*fwd_args, sa), "sil_fwd")      # (no successor on the side stream: see side_own_vo)
+                ck(sctx.forward(**fwd_args), "sil_fwd")      # (no successor on the side stream: see side_own_vo)
             else:
                 # the face setup (which also writes the camera-space vertices self.vo), the fork of the side stream, then the
                 # rasteriser: the pair-wise losses do not wait for the raster and the raster has one successor on its chain
-                ck(L.hm_sil_fwd_phase_clips(*fwd_args, 1, sa), "sil_fwd(setup)")
+                ck(sctx.forward(phases=1, **fwd_args), "sil_fwd(setup)")
                 self.ev_sil.record(main)
-                ck(L.hm_sil_fwd_phase_clips(*fwd_args, 2, sa), "sil_fwd(raster)")
+                ck(sctx.forward(phases=2, **fwd_args), "sil_fwd(raster)")
                 if use_aux:
                     self.ev_ras.record(main)     # the tile partials of the fused loss, for the reduction on the third stream
             if on["depth"] and not self.merge_renders:
                 # the OBJECT's depth render of the ordinal depth term rides this chain, right behind the silhouette raster (its
                 # vertices are the face setup's): the hand's render runs on the side stream meanwhile - two renders after each
                 # other there made the hand side twice as long as this chain
-                self._depth_render(self.vo, self.dctx[0], Vo, self.d_sil_o, self.d_dep_o, sa)
+                self._depth_render(self.vo, self.dctx[0], self.d_sil_o, self.d_dep_o, sa)
                 self.ev_dep.record(main)
-            bwd_args = (P(self.vo), P(self.sil_K), B, Vo, sctx.F, sctx.S, 1.0, self.sil_eps,
-                        2 if self.lw["lw_sil_obj"] > 0 else 1,
-                        P(self.up_sil), None, P(m.keep_sum), P(sctx.adj_off), P(sctx.adj_items),
-                        P(sctx.face_order), None, None, P(sctx.workspace), CL,
-                        self._slot("loss_sil_obj") if self.sil_reduce_in_bwd else None, NS)
-            q2 = sctx.sum_log2q          # grid of the order-independent sums (the same for the sweeps and the rigid backward)
             # (no vertex gather; the loss / IoU values come out of its first launch)
+            bwd_args = dict(upstream=self.up_sil, keep_sum=m.keep_sum, clip_len=CL,
+                            loss_out=self._slot("loss_sil_obj") if self.sil_reduce_in_bwd else None, out_stride=NS, stream=sa)
+            mode = 2 if self.lw["lw_sil_obj"] > 0 else 1
             if self.pairs_after_lines:
                 # a clip batch: the line expansion - latency-bound, and the kernel of this chain that suffers most from
                 # neighbours holding its wave slots - runs ALONE; the pair-wise terms of the side stream wait for its end
-                ck(L.hm_sil_bwd_phase_clips(*bwd_args, 1, q2, sa), "sil_bwd(lines)")
+                ck(sctx.backward(self.vo, self.sil_K, mode, phases=1, **bwd_args), "sil_bwd(lines)")
                 self.ev_lines.record(main)
-                ck(L.hm_sil_bwd_phase_clips(*bwd_args, 2, q2, sa), "sil_bwd(sweeps)")
+                ck(sctx.backward(self.vo, self.sil_K, mode, phases=2, **bwd_args), "sil_bwd(sweeps)")
             else:
-                ck(L.hm_sil_bwd_clips(*bwd_args, q2, sa), "sil_bwd")
+                ck(sctx.backward(self.vo, self.sil_K, mode, **bwd_args), "sil_bwd")
 
     def _issue_hand_forward(self, it):
         """B: object / hand vertices, the hand-only terms, then the waits that place the pair-wise terms next to the silhouette chain"""
@@ -758,11 +749,11 @@ class FusedStepper:
         if on["depth"]:
             ctx_o, ctx_h, m_o, m_h = self.dctx
             Sd, K = ctx_o.S, P(m.camintr)
-            self._depth_render(self.vh, ctx_h, Vh, self.d_sil_h, self.d_dep_h, sb)
+            self._depth_render(self.vh, ctx_h, self.d_sil_h, self.d_dep_h, sb)
             if on["sil"]:
                 side.wait_event(self.ev_dep)        # the object's depth image, from the calling stream
             else:
-                self._depth_render(self.vo, ctx_o, Vo, self.d_sil_o, self.d_dep_o, sb)
+                self._depth_render(self.vo, ctx_o, self.d_sil_o, self.d_dep_o, sb)
             rw_bytes = L.hm_reduce_workspace_bytes()
             for ci in range(C):           # per clip: the term normalises over the clip's own pairs and mask counts
                 fr = slice(ci * CL, (ci + 1) * CL)
@@ -851,7 +842,7 @@ class FusedStepper:
                                  (self.G_dep_o if on["depth"] else None, 1.0)])
         if on["sil"]:       # the silhouette term is gathered from the sweeps' per-corner gradients inside this launch
             ck(L.hm_rigid_bwd_sil_clips(P(m.verts_object_og), P(m.rotations_object), P(m.int_scales_object), 1, tp, tw, tn,
-                                        L.hm_sil_parts(P(sctx.workspace), B, Vo, sctx.F, sctx.S), P(sctx.adj_off),
+                                        sctx.parts_ptr(), P(sctx.adj_off),
                                         P(sctx.adj_items), P(self.vo), P(self.sil_K), 1.0, sctx.F, B, Vo,
                                         P(m.rotations_object.grad), P(m.translations_object.grad),
                                         P(self.g_so_part) if sc_obj else None, P(self.rigid_ws_o), CL, sctx.sum_log2q,
@@ -890,27 +881,22 @@ class FusedStepper:
     def sil_chain_only(self):
         """Measurement helper (tools/bench_sil_kernels.py --chain): just the silhouette chain of an iteration - face setup,
         raster, lines, sweeps - on the current stream, with nothing on any other stream."""
-        m, L, P, ck = self.model, self.L, _lib.ptr, _lib.check
-        sctx, B, Vo, CL, NS = m.sil_ctx, self.B, self.Vo, self.clip_len, self.NS
+        m, ck = self.model, _lib.check
+        sctx, CL, NS = m.sil_ctx, self.clip_len, self.NS
         sa = torch.cuda.current_stream().cuda_stream
-        ck(L.hm_sil_fwd_clips(P(m.verts_object_og), P(sctx.faces), 0, P(self.sil_K), B, Vo, sctx.F, sctx.S,
-                              1.0, self.ops.NMR_NEAR, self.ops.NMR_FAR, P(self.sil_keep), P(self.sil_ref),
-                              None, P(self.pooled), None, P(sctx.work_order), None, None, 0, P(m.rotations_object),
-                              P(m.translations_object), P(m.int_scales_object), 1, 1, P(sctx.workspace), CL, NS, P(self.vo),
-                              sa), "sil_fwd")
-        ck(L.hm_sil_bwd_clips(P(self.vo), P(self.sil_K), B, Vo, sctx.F, sctx.S, 1.0, self.sil_eps, 2,
-                              P(self.up_sil), None, P(m.keep_sum), P(sctx.adj_off), P(sctx.adj_items), P(sctx.face_order),
-                              None, None, P(sctx.workspace), CL, None, NS, sctx.sum_log2q, sa), "sil_bwd")
+        ck(sctx.forward(verts=m.verts_object_og, K=self.sil_K, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
+                        rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object, rigid_scale=m.int_scales_object,
+                        rigid_abs=1, persistent_outputs=1, clip_len=CL, cam_verts_out=self.vo, out_stride=NS, stream=sa), "sil_fwd")
+        ck(sctx.backward(self.vo, self.sil_K, 2, upstream=self.up_sil, keep_sum=m.keep_sum, clip_len=CL, out_stride=NS, stream=sa),
+           "sil_bwd")
 
-    def _depth_render(self, verts, ctx, V_, sil, dep, stream_id):
+    def _depth_render(self, verts, ctx, sil, dep, stream_id):
         """depth + silhouette images of one mesh at the full-image camera (reference homan.py:391,406), all frames.  The
         renders write into buffers this stepper owns and keeps passing: a region that is empty again leaves the empty pattern it
         wrote last time alone (hm_sil_fwd's persistent_outputs, as the silhouette render does) - at the full-image camera nine
         regions in ten are background"""
-        m, L, P = self.model, self.L, _lib.ptr
-        _lib.check(L.hm_sil_fwd(P(verts), P(ctx.faces), 0, P(m.camintr), self.B, V_, ctx.F, ctx.S, 1.0, self.ops.NMR_NEAR,
-                                self.ops.NMR_FAR, None, None, None, P(sil), None, P(ctx.work_order), P(dep), None, 0, None, None,
-                                None, 0, 1, P(ctx.workspace), stream_id), "depth render")
+        _lib.check(ctx.forward(verts=verts, K=self.model.camintr, pooled=sil, pooled_depth=dep, persistent_outputs=1,
+                               stream=stream_id), "depth render")
 
     def _adam_log(self):
         if not self.log_in_adam:

@@ -27,17 +27,14 @@ def forward_backward_hands(self, log=False):
     side.wait_stream(main)
     # ---------------- A: silhouettes forward + backward (as in the one-hand sequence)
     if on["sil"]:
-        fwd_args = (P(m.verts_object_og), P(sctx.faces), 0, P(self.sil_K), B, Vo, sctx.F, sctx.S,
-                    1.0, self.ops.NMR_NEAR, self.ops.NMR_FAR, P(self.sil_keep), P(self.sil_ref),
-                    None, P(self.pooled), None, P(sctx.work_order), None, None, 0, P(m.rotations_object),
-                    P(m.translations_object), P(m.int_scales_object), 1, 1, P(sctx.workspace), 0, NS, P(self.vo))
-        ck(L.hm_sil_fwd_phase_clips(*fwd_args, 1, sa), "sil_fwd(setup)")
+        fwd_args = dict(verts=m.verts_object_og, K=self.sil_K, keep=self.sil_keep, ref=self.sil_ref, pooled=self.pooled,
+                        rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object, rigid_scale=m.int_scales_object,
+                        rigid_abs=1, persistent_outputs=1, clip_len=0, cam_verts_out=self.vo, out_stride=NS, stream=sa)
+        ck(sctx.forward(phases=1, **fwd_args), "sil_fwd(setup)")
         self.ev_sil.record(main)
-        ck(L.hm_sil_fwd_phase_clips(*fwd_args, 2, sa), "sil_fwd(raster)")
-        ck(L.hm_sil_bwd_clips(P(self.vo), P(self.sil_K), B, Vo, sctx.F, sctx.S, 1.0, self.sil_eps,
-                              2 if self.lw["lw_sil_obj"] > 0 else 1, P(self.up_sil), None, P(m.keep_sum),
-                              P(sctx.adj_off), P(sctx.adj_items), P(sctx.face_order), None, None, P(sctx.workspace), 0,
-                              slot("loss_sil_obj"), NS, sctx.sum_log2q, sa), "sil_bwd")
+        ck(sctx.forward(phases=2, **fwd_args), "sil_fwd(raster)")
+        ck(sctx.backward(self.vo, self.sil_K, 2 if self.lw["lw_sil_obj"] > 0 else 1, upstream=self.up_sil, keep_sum=m.keep_sum,
+                         clip_len=0, loss_out=slot("loss_sil_obj"), out_stride=NS, stream=sa), "sil_bwd")
     # ---------------- B: hands
     with torch.cuda.stream(side):
         if not on["sil"]:
@@ -104,7 +101,7 @@ def forward_backward_hands(self, log=False):
             Sd, K = self.dlayers[0][0].S, P(m.camintr)
             lverts = [self.vo] + list(self.vh_d)
             for li, (ctx, V_, _) in enumerate(self.dlayers):
-                self._depth_render(lverts[li], ctx, V_, self.dl_sil[li], self.dl_dep[li], sb)
+                self._depth_render(lverts[li], ctx, self.dl_sil[li], self.dl_dep[li], sb)
             for k, (a, b) in enumerate(self.dpairs):
                 ck(L.hm_ordinal_depth_fwd(P(self.dl_dep[a]), P(self.dl_dep[b]), P(self.dl_sil[a]), P(self.dl_sil[b]),
                                           P(self.dlayers[a][2]), P(self.dlayers[b][2]), B, Sd, P(self.dp_part[k]),
@@ -186,7 +183,7 @@ def forward_backward_hands(self, log=False):
                              (self.G_dep_o if on["depth"] else None, 1.0)])
     if on["sil"]:
         ck(L.hm_rigid_bwd_sil_clips(P(m.verts_object_og), P(m.rotations_object), P(m.int_scales_object), 1, tp, tw, tn,
-                                    L.hm_sil_parts(P(sctx.workspace), B, Vo, sctx.F, sctx.S), P(sctx.adj_off),
+                                    sctx.parts_ptr(), P(sctx.adj_off),
                                     P(sctx.adj_items), P(self.vo), P(self.sil_K), 1.0, sctx.F, B, Vo,
                                     P(m.rotations_object.grad), P(m.translations_object.grad),
                                     P(self.g_so_part) if sc_obj else None, P(self.rigid_ws_o), 0, sctx.sum_log2q, None, 0.0, sa),

@@ -16,6 +16,14 @@ def _f32(t):
     return t.contiguous().float()
 
 
+def _p(v):
+    """what a C argument takes: a tensor's device address; None, numbers and raw addresses as they are"""
+    return _lib.ptr(v) if isinstance(v, torch.Tensor) else v
+
+
+_RENDER_FIELDS = {name for name, _ in _lib.SilRender._fields_}
+
+
 def build_adjacency(faces_np, num_verts):
     """CSR vertex -> (face*3 + corner) lists for a (F,3) face array (host, once per topology)."""
     faces_np = np.asarray(faces_np).astype(np.int64)
@@ -57,7 +65,6 @@ class SilhouetteContext:
         regions = np.argsort(ring, kind="stable").astype(np.int64)
         wo = (np.arange(batch, dtype=np.int64)[None, :] << 16) | regions[:, None]
         self.work_order = torch.from_numpy(wo.reshape(-1).astype(np.int32)).to(device)
-        self.face_order = None
         # grid of the backward's order-independent sums (include/homan_amd.h, "ORDER-INDEPENDENT SUMS"): 0 = the default
         # 2^-44, right for the normalised silhouette loss of the joint fit; the pose initialisation's unnormalised sums of
         # squares set a coarser one
@@ -134,7 +141,47 @@ class SilhouetteContext:
         self.near_winding = near
         # (the edge sweeps keep the natural face order: sorting faces by box perimeter was measured slower -- it scatters
         #  neighbouring faces, and with them the cache lines of the index map and the mask planes they share)
-        self.face_order = None
+
+    # ---- the rasteriser's launches (include/homan_amd.h; keywords = the header's parameter names = HmSilRender's fields).  A launch
+    # layer only: K, masks and gradient images arrive as the kernels take them (K_eff / pad / crop stay with the caller), and the
+    # library's return code goes back to the caller, who hands it to lib.check under its own label
+    def render_fields(self, **given):
+        """the HmSilRender fields of one render on this context (lib.sil_renders): the context's own state + `given`"""
+        unknown = set(given) - _RENDER_FIELDS
+        if unknown:
+            raise TypeError(f"render_fields: unknown field(s) {sorted(unknown)}")
+        return dict(faces=self.faces, faces_bstride=0, B=self.B, V=self.V, F=self.F, S=self.S, znear=NMR_NEAR, zfar=NMR_FAR,
+                    orig_size=1.0, work_order=self.work_order, workspace=self.workspace) | given
+
+    def forward(self, *, keep_sum=None, loss_out=None, alpha_full=None, out_stride=0, phases=3, stream=None, **render):
+        """one hm_sil_fwd_phase_clips: `render` as render_fields takes it (verts, K, pooled required)"""
+        r = {k: _p(v) for k, v in self.render_fields(**render).items()}
+        g = r.get
+        return _lib.lib().hm_sil_fwd_phase_clips(
+            r["verts"], r["faces"], r["faces_bstride"], r["K"], r["B"], r["V"], r["F"], r["S"], float(r["orig_size"]), r["znear"],
+            r["zfar"], g("keep"), g("ref"), _p(keep_sum), r["pooled"], _p(loss_out), r["work_order"], g("pooled_depth"),
+            _p(alpha_full), g("mask_shared", 0), g("rigid_rot6d"), g("rigid_trans"), g("rigid_scale"), g("rigid_abs", 0),
+            g("persistent_outputs", 0), r["workspace"], g("clip_len", 0), out_stride, g("cam_verts_out"), phases,
+            _lib.stream() if stream is None else stream)
+
+    def backward(self, verts, K, mode, *, upstream=None, grad_pooled=None, keep_sum=None, grad_verts=None, grad_ndc=None,
+                 clip_len=0, loss_out=None, out_stride=0, phases=3, eps=None, sum_log2q=None, orig_size=1.0, stream=None):
+        """one hm_sil_bwd_phase_clips on the state the last forward left in the workspace"""
+        return _lib.lib().hm_sil_bwd_phase_clips(
+            _p(verts), _p(K), self.B, self.V, self.F, self.S, float(orig_size), self.eps() if eps is None else eps, mode,
+            _p(upstream), _p(grad_pooled), _p(keep_sum), _p(self.adj_off), _p(self.adj_items), _p(grad_verts), _p(grad_ndc),
+            _p(self.workspace), clip_len, _p(loss_out), out_stride, phases, self.sum_log2q if sum_log2q is None else sum_log2q,
+            _lib.stream() if stream is None else stream)
+
+    def reduce(self, *, keep_sum=None, loss_out=None, frame_out=None, clip_len=0, out_stride=0, stream=None):
+        """one hm_sil_reduce_clips"""
+        return _lib.lib().hm_sil_reduce_clips(self.B, self.V, self.F, self.S, _p(keep_sum), _p(loss_out), _p(frame_out),
+                                              _p(self.workspace), clip_len, out_stride,
+                                              _lib.stream() if stream is None else stream)
+
+    def parts_ptr(self):
+        """device address of the (B,F,3,2) doubles of the last backward: the `sil_parts` of hm_rigid_bwd_sil*"""
+        return _lib.lib().hm_sil_parts(_p(self.workspace), self.B, self.V, self.F, self.S)
 
     def idx_map(self):
         out = torch.empty(self.B, 2 * self.S, 2 * self.S, dtype=torch.int32, device=self.workspace.device)
@@ -170,12 +217,8 @@ class _SilhouetteLoss(torch.autograd.Function):
         keep, ref = sctx.pad(keep), sctx.pad(ref)          # (padding: keep = 0, so it counts for nothing)
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
         out = torch.empty(2, device=verts.device)
-        _lib.check(_lib.lib().hm_sil_fwd(
-            _lib.ptr(verts), _lib.ptr(sctx.faces), 0, _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S,
-            float(orig_size), NMR_NEAR, NMR_FAR, _lib.ptr(keep), _lib.ptr(ref), _lib.ptr(keep_sum),
-            _lib.ptr(pooled), _lib.ptr(out), _lib.ptr(sctx.work_order), None, None, 0, None, None, None, 0, 0,
-            _lib.ptr(sctx.workspace), _lib.stream()),
-            "hm_sil_fwd")
+        _lib.check(sctx.forward(verts=verts, K=K, orig_size=orig_size, keep=keep, ref=ref, keep_sum=keep_sum, pooled=pooled,
+                                loss_out=out), "hm_sil_fwd")
         ctx.save_for_backward(verts, K, keep_sum)
         ctx.sctx, ctx.orig_size = sctx, orig_size
         pooled = sctx.crop(pooled)
@@ -188,10 +231,8 @@ class _SilhouetteLoss(torch.autograd.Function):
         sctx = ctx.sctx
         g_loss = _f32(g_loss).reshape(1)
         grad_verts = torch.empty_like(verts)
-        _lib.check(_lib.lib().hm_sil_bwd(
-            _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size), sctx.eps(), 1,
-            _lib.ptr(g_loss), None, _lib.ptr(keep_sum), _lib.ptr(sctx.adj_off), _lib.ptr(sctx.adj_items),
-            _lib.ptr(sctx.face_order), _lib.ptr(grad_verts), None, _lib.ptr(sctx.workspace), sctx.sum_log2q, _lib.stream()), "hm_sil_bwd")
+        _lib.check(sctx.backward(verts, K, 1, upstream=g_loss, keep_sum=keep_sum, grad_verts=grad_verts,
+                                 orig_size=ctx.orig_size), "hm_sil_bwd")
         return grad_verts, None, None, None, None, None, None
 
 
@@ -202,11 +243,7 @@ class _SilhouetteRender(torch.autograd.Function):
     def forward(ctx, verts, K, sctx, orig_size):
         verts, K = _f32(verts), sctx.K_eff(_f32(K))
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
-        _lib.check(_lib.lib().hm_sil_fwd(
-            _lib.ptr(verts), _lib.ptr(sctx.faces), 0, _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S,
-            float(orig_size), NMR_NEAR, NMR_FAR, None, None, None, _lib.ptr(pooled), None,
-            _lib.ptr(sctx.work_order), None, None, 0, None, None, None, 0, 0, _lib.ptr(sctx.workspace), _lib.stream()),
-            "hm_sil_fwd")
+        _lib.check(sctx.forward(verts=verts, K=K, orig_size=orig_size, pooled=pooled), "hm_sil_fwd")
         ctx.save_for_backward(verts, K)
         ctx.sctx, ctx.orig_size = sctx, orig_size
         return sctx.crop(pooled)
@@ -217,11 +254,8 @@ class _SilhouetteRender(torch.autograd.Function):
         sctx = ctx.sctx
         g_img = sctx.pad(_f32(g_img))
         grad_verts = torch.empty_like(verts)
-        _lib.check(_lib.lib().hm_sil_bwd(
-            _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size), sctx.eps(), 0,
-            None, _lib.ptr(g_img), None, _lib.ptr(sctx.adj_off), _lib.ptr(sctx.adj_items),
-            _lib.ptr(sctx.face_order), _lib.ptr(grad_verts), _lib.ptr(sctx.grad_ndc) if getattr(sctx, "grad_ndc", None) is not None else None,
-            _lib.ptr(sctx.workspace), sctx.sum_log2q, _lib.stream()), "hm_sil_bwd")
+        _lib.check(sctx.backward(verts, K, 0, grad_pooled=g_img, grad_verts=grad_verts, grad_ndc=getattr(sctx, "grad_ndc", None),
+                                 orig_size=ctx.orig_size), "hm_sil_bwd")
         return grad_verts, None, None, None
 
 
@@ -236,11 +270,7 @@ class _SilhouetteRenderNoAA(torch.autograd.Function):
         n = 2 * sctx.S
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
         alpha = torch.empty(sctx.B, n, n, device=verts.device)
-        _lib.check(_lib.lib().hm_sil_fwd(
-            _lib.ptr(verts), _lib.ptr(sctx.faces), 0, _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S,
-            float(orig_size), NMR_NEAR, NMR_FAR, None, None, None, _lib.ptr(pooled), None,
-            _lib.ptr(sctx.work_order), None, _lib.ptr(alpha), 0, None, None, None, 0, 0, _lib.ptr(sctx.workspace),
-            _lib.stream()), "hm_sil_fwd")
+        _lib.check(sctx.forward(verts=verts, K=K, orig_size=orig_size, pooled=pooled, alpha_full=alpha), "hm_sil_fwd")
         ctx.save_for_backward(verts, K)
         ctx.sctx, ctx.orig_size = sctx, orig_size
         return sctx.crop_samples(alpha)
@@ -251,10 +281,7 @@ class _SilhouetteRenderNoAA(torch.autograd.Function):
         sctx = ctx.sctx
         g_img = sctx.pad_samples(_f32(g_img))
         grad_verts = torch.empty_like(verts)
-        _lib.check(_lib.lib().hm_sil_bwd(
-            _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size), sctx.eps(), 3,
-            None, _lib.ptr(g_img), None, _lib.ptr(sctx.adj_off), _lib.ptr(sctx.adj_items),
-            _lib.ptr(sctx.face_order), _lib.ptr(grad_verts), None, _lib.ptr(sctx.workspace), sctx.sum_log2q, _lib.stream()), "hm_sil_bwd")
+        _lib.check(sctx.backward(verts, K, 3, grad_pooled=g_img, grad_verts=grad_verts, orig_size=ctx.orig_size), "hm_sil_bwd")
         return grad_verts, None, None, None
 
 
@@ -277,13 +304,9 @@ class _MaskedSilhouetteL2NoAA(torch.autograd.Function):
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
         alpha = torch.empty(sctx.B, n, n, device=verts.device)
         frame = torch.empty(sctx.B, 2, device=verts.device)
-        _lib.check(_lib.lib().hm_sil_fwd(
-            _lib.ptr(verts), _lib.ptr(sctx.faces), 0, _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S,
-            float(orig_size), NMR_NEAR, NMR_FAR, _lib.ptr(keep), _lib.ptr(ref), None, _lib.ptr(pooled), None,
-            _lib.ptr(sctx.work_order), None, _lib.ptr(alpha), 1, None, None, None, 0, 0, _lib.ptr(sctx.workspace),
-            _lib.stream()), "hm_sil_fwd")
-        _lib.check(_lib.lib().hm_sil_reduce(sctx.B, sctx.V, sctx.F, sctx.S, None, None, _lib.ptr(frame),
-                                            _lib.ptr(sctx.workspace), _lib.stream()), "hm_sil_reduce")
+        _lib.check(sctx.forward(verts=verts, K=K, orig_size=orig_size, keep=keep, ref=ref, mask_shared=1, pooled=pooled,
+                                alpha_full=alpha), "hm_sil_fwd")
+        _lib.check(sctx.reduce(frame_out=frame), "hm_sil_reduce")
         ctx.save_for_backward(verts, K)
         ctx.sctx, ctx.orig_size = sctx, orig_size
         alpha = sctx.crop_samples(alpha)
@@ -296,10 +319,7 @@ class _MaskedSilhouetteL2NoAA(torch.autograd.Function):
         sctx = ctx.sctx
         g_loss = _f32(g_loss).contiguous()
         grad_verts = torch.empty_like(verts)
-        _lib.check(_lib.lib().hm_sil_bwd(
-            _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size), sctx.eps(), 4,
-            _lib.ptr(g_loss), None, None, _lib.ptr(sctx.adj_off), _lib.ptr(sctx.adj_items),
-            _lib.ptr(sctx.face_order), _lib.ptr(grad_verts), None, _lib.ptr(sctx.workspace), sctx.sum_log2q, _lib.stream()), "hm_sil_bwd")
+        _lib.check(sctx.backward(verts, K, 4, upstream=g_loss, grad_verts=grad_verts, orig_size=ctx.orig_size), "hm_sil_bwd")
         return grad_verts, None, None, None, None, None
 
 
@@ -385,12 +405,7 @@ class _DepthRender(torch.autograd.Function):
         verts, K = _f32(verts), sctx.K_eff(_f32(K))
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
         depth = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
-        _lib.check(_lib.lib().hm_sil_fwd(
-            _lib.ptr(verts), _lib.ptr(sctx.faces), 0, _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S,
-            float(orig_size), NMR_NEAR, NMR_FAR, None, None, None, _lib.ptr(pooled), None,
-            _lib.ptr(sctx.work_order), _lib.ptr(depth), None, 0, None, None, None, 0, 0, _lib.ptr(sctx.workspace),
-            _lib.stream()),
-            "hm_sil_fwd")
+        _lib.check(sctx.forward(verts=verts, K=K, orig_size=orig_size, pooled=pooled, pooled_depth=depth), "hm_sil_fwd")
         ctx.save_for_backward(verts, K)
         ctx.sctx, ctx.orig_size = sctx, orig_size
         pooled, depth = sctx.crop(pooled), sctx.crop(depth)

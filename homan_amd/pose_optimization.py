@@ -317,7 +317,7 @@ class _FusedPoseLoop:
         pooled, frame = f(n, S, S), f(n, 2)
         # (views of the model's own tensors when the mask size lies on the kernels' tile grid, copies otherwise: refresh())
         self.keep, self.ref = sctx.pad_samples(model._keep1).contiguous(), sctx.pad_samples(model._ref1).contiguous()
-        self.K_all, self.K_one, eps = sctx.K_eff(model._K_all).contiguous(), model.K[0].contiguous(), sctx.eps()
+        self.K_all, self.K_one = sctx.K_eff(model._K_all).contiguous(), model.K[0].contiguous()
         keep, ref, K_all, K_one = self.keep, self.ref, self.K_all, self.K_one
         ones = torch.ones(n, device=dev)
         rws = torch.zeros(L.hm_rigid_workspace_bytes(n), dtype=torch.uint8, device=dev)
@@ -335,61 +335,40 @@ class _FusedPoseLoop:
         self._keepalive = (verts, g_off, off, pooled, frame, ones, rws, tp, tw)
         self.edge = edge = _EdgeTermBuffers(model, self.ref) if model.lw_chamfer != 0 else None
 
-        def edge_step():
-            """the step with the edge-chamfer term: same chain, the loss and its per-sample gradient from hm_pose_edge_terms"""
-            st = _lib.stream()
-            ck(L.hm_rigid_fwd(P(model.vertices), P(model.rotations), P(model.translations), P(model._one), 0, n, V, None, P(verts),
-                              st), "hm_rigid_fwd")
-            ck(L.hm_offscreen_fwd(P(verts), P(K_one), n, V, NMR_FAR, 100000.0, P(off), P(g_off), st), "hm_offscreen_fwd")
-            ck(L.hm_sil_fwd(P(verts), P(sctx.faces), 0, P(K_all), n, V, F, S, 1.0, ops.NMR_NEAR, ops.NMR_FAR, None, None, None,
-                            P(pooled), None, P(sctx.work_order), None, P(edge.alpha), 0, None, None, None, 0, 0, P(sctx.workspace),
-                            st), "hm_sil_fwd")
-            ck(L.hm_pose_edge_terms(P(edge.alpha), P(keep), P(ref), P(edge.edt), n, edge.size, 2 * S, edge.kernel_size,
-                                    float(model.lw_chamfer), P(edge.terms), P(edge.grad), P(edge.workspace), st),
-               "hm_pose_edge_terms")
-            ck(L.hm_sil_bwd(P(verts), P(K_all), n, V, F, S, 1.0, eps, 3, None, P(edge.grad), None, P(sctx.adj_off),
-                            P(sctx.adj_items), P(sctx.face_order), None, None, P(sctx.workspace), edge.sum_log2q, st), "hm_sil_bwd")
-            ck(L.hm_rigid_bwd_sil(P(model.vertices), P(model.rotations), P(model._one), 0, tp, tw, tn,
-                                  L.hm_sil_parts(P(sctx.workspace), n, V, F, S), P(sctx.adj_off), P(sctx.adj_items), P(verts),
-                                  P(K_all), 1.0, F, n, V, P(model.rotations.grad), P(model.translations.grad), None, P(rws),
-                                  edge.sum_log2q, st),
-               "hm_rigid_bwd_sil")
-            opt.step(zero_grad=False)
-            # (mask + chamfer) + offscreen, the order of sum(loss_dict.values()): terms[:, 0] holds the first sum
-            if log is not None:
-                ck(L.hm_pose_keep_best_log(P(edge.terms), 4, P(off), n, P(model.rotations), P(model.translations), P(opt.step_t),
-                                           self.log_steps, P(log), P(losses_out), st), "hm_pose_keep_best_log")
-            else:
-                ck(L.hm_pose_keep_best(P(edge.terms), 4, P(off), n, P(model.rotations), P(model.translations), P(best_loss),
-                                       P(best_rot), P(best_trans), P(losses_out), st), "hm_pose_keep_best")
+        # one binary mask for every candidate and no per-sample outputs (mask_shared = 1 | 2, see include/homan_amd.h) - or, with the
+        # edge-chamfer term, the un-pooled coverage for hm_pose_edge_terms, which forms the loss and its per-sample gradient
+        raster = dict(alpha_full=edge.alpha) if edge is not None else dict(keep=keep, ref=ref, mask_shared=3)
+        bwd = (dict(mode=3, grad_pooled=edge.grad, sum_log2q=edge.sum_log2q) if edge is not None else
+               dict(mode=5, upstream=ones, sum_log2q=sctx.sum_log2q))
+        sums, stride = (edge.terms, 4) if edge is not None else (frame, 2)
 
         def step():
             st = _lib.stream()
             ck(L.hm_rigid_fwd(P(model.vertices), P(model.rotations), P(model.translations), P(model._one), 0, n, V, None, P(verts),
                               st), "hm_rigid_fwd")
             ck(L.hm_offscreen_fwd(P(verts), P(K_one), n, V, NMR_FAR, 100000.0, P(off), P(g_off), st), "hm_offscreen_fwd")
-            # (mask_shared = 1 | 2: one binary mask for every candidate, no per-sample outputs - see include/homan_amd.h)
-            ck(L.hm_sil_fwd(P(verts), P(sctx.faces), 0, P(K_all), n, V, F, S, 1.0, ops.NMR_NEAR, ops.NMR_FAR, P(keep), P(ref), None,
-                            P(pooled), None, P(sctx.work_order), None, None, 3, None, None, None, 0, 0, P(sctx.workspace), st),
-               "hm_sil_fwd")
-            ck(L.hm_sil_reduce(n, V, F, S, None, None, P(frame), P(sctx.workspace), st), "hm_sil_reduce")
-            ck(L.hm_sil_bwd(P(verts), P(K_all), n, V, F, S, 1.0, eps, 5, P(ones), None, None, P(sctx.adj_off), P(sctx.adj_items),
-                            P(sctx.face_order), None, None, P(sctx.workspace), sctx.sum_log2q, st), "hm_sil_bwd")
-            ck(L.hm_rigid_bwd_sil(P(model.vertices), P(model.rotations), P(model._one), 0, tp, tw, tn,
-                                  L.hm_sil_parts(P(sctx.workspace), n, V, F, S), P(sctx.adj_off), P(sctx.adj_items), P(verts),
-                                  P(K_all), 1.0, F, n, V, P(model.rotations.grad), P(model.translations.grad), None, P(rws),
-                                  sctx.sum_log2q, st),
-               "hm_rigid_bwd_sil")
+            ck(sctx.forward(verts=verts, K=K_all, pooled=pooled, stream=st, **raster), "hm_sil_fwd")
+            if edge is not None:
+                ck(L.hm_pose_edge_terms(P(edge.alpha), P(keep), P(ref), P(edge.edt), n, edge.size, 2 * S, edge.kernel_size,
+                                        float(model.lw_chamfer), P(edge.terms), P(edge.grad), P(edge.workspace), st),
+                   "hm_pose_edge_terms")
+            else:
+                ck(sctx.reduce(frame_out=frame, stream=st), "hm_sil_reduce")
+            ck(sctx.backward(verts, K_all, stream=st, **bwd), "hm_sil_bwd")
+            ck(L.hm_rigid_bwd_sil(P(model.vertices), P(model.rotations), P(model._one), 0, tp, tw, tn, sctx.parts_ptr(),
+                                  P(sctx.adj_off), P(sctx.adj_items), P(verts), P(K_all), 1.0, F, n, V, P(model.rotations.grad),
+                                  P(model.translations.grad), None, P(rws), bwd["sum_log2q"], st), "hm_rigid_bwd_sil")
             opt.step(zero_grad=False)
-            # mask + (chamfer = 0) + offscreen, the order of sum(loss_dict.values()); best-ever bookkeeping in the same launch
+            # mask + chamfer + offscreen, the order of sum(loss_dict.values()): terms[:, 0] holds the first sum, frame[:, 0] the mask
+            # term alone (chamfer = 0); best-ever bookkeeping in the same launch
             if log is not None:
-                ck(L.hm_pose_keep_best_log(P(frame), 2, P(off), n, P(model.rotations), P(model.translations), P(opt.step_t),
+                ck(L.hm_pose_keep_best_log(P(sums), stride, P(off), n, P(model.rotations), P(model.translations), P(opt.step_t),
                                            self.log_steps, P(log), P(losses_out), st), "hm_pose_keep_best_log")
             else:
-                ck(L.hm_pose_keep_best(P(frame), 2, P(off), n, P(model.rotations), P(model.translations), P(best_loss), P(best_rot),
-                                       P(best_trans), P(losses_out), st), "hm_pose_keep_best")
+                ck(L.hm_pose_keep_best(P(sums), stride, P(off), n, P(model.rotations), P(model.translations), P(best_loss),
+                                       P(best_rot), P(best_trans), P(losses_out), st), "hm_pose_keep_best")
 
-        self._step = step if edge is None else edge_step
+        self._step = step
         self.graph = None
         if edge is not None:
             edge.refresh()

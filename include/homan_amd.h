@@ -115,16 +115,8 @@ int hm_edge_edt(const float* ref, int size, int stride, int kernel_size, float p
 size_t hm_pose_edge_workspace_bytes(int N, int stride);
 int hm_pose_edge_terms(const float* alpha, const float* keep, const float* ref, const float* edt, int N, int size, int stride,
                        int kernel_size, float lw_chamfer, float* terms, float* grad, void* workspace, hipStream_t stream);
-/* out = s[0] * in ;  out = s0[0]*a + s1[0]*b   (backward of the losses whose unit gradient is produced forward) */
+/* out = s[0] * in   (backward of the losses whose unit gradient is produced forward) */
 int hm_scale_by(const float* in, const float* s, long n, float* out, hipStream_t stream);
-int hm_scale2_by(const float* a, const float* s0, const float* b, const float* s1, long n, float* out,
-                 hipStream_t stream);
-/* out = w0*a0 + w1*a1 + w2*a2 + w3*a3 (NULL terms skipped): the weighted sum of per-loss vertex gradients, i.e. the
- * `loss = sum_k lw_k * loss_k` weighting of reference homan/jointopt.py:180-188 applied to gradients. */
-int hm_lincomb4(const float* a0, float w0, const float* a1, float w1, const float* a2, float w2, const float* a3,
-                float w3, long n, float* out, hipStream_t stream);
-/* out[0] = w0 * sum(parts[0..n)) + w1 * extra[0]  (extra may be NULL) */
-int hm_sum_small(const float* parts, int n, float w0, const float* extra, float w1, float* out, hipStream_t stream);
 
 /* ------------------------------------------------------------------ MANO linear blend skinning
  * reference homan/manomodel.py:84-151 (ManoModel.forward_pca, right hand) + the `mano` layer it calls
@@ -205,12 +197,11 @@ int hm_sil_reduce(int B, int V, int F, int S, const float* keep_sum, float* loss
  *   covered one that pushes, so the line pass reads no per-sample gradient (same results as mode 4 on such masks, bit for bit).
  * mode 1: upstream (1) = dL/d loss_out[0]; mode 2: same with upstream[0] > 0 guaranteed by the caller (the forward's
  * sweep planes are reused, one launch less); mode 0: grad_pooled (B,S,S) = dL/d pooled.  adj_off (V+1), adj_items (3F):
- * CSR vertex -> (face*3 + corner).  face_order: B*F int32 permutation of frame*F+face (visiting order of the edge
- * sweeps, expensive faces first) or NULL.  grad_verts (B,V,3) overwritten, or NULL to skip the vertex gather (the
+ * CSR vertex -> (face*3 + corner).  grad_verts (B,V,3) overwritten, or NULL to skip the vertex gather (the
  * per-corner gradients stay in the workspace: hm_sil_parts / hm_rigid_bwd_sil); grad_ndc (B,V,3) optional. */
 int hm_sil_bwd(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-               const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+               const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                int sum_log2q, hipStream_t stream);
 /* Backward of the depth image (neural_renderer backward_depth_map, reached from reference homan/homan.py:391,406):
  * grad_pooled_depth (B,S,S) -> grad_verts (B,V,3), for the frame state the last hm_sil_fwd left in `workspace`. */
@@ -326,11 +317,6 @@ int hm_smooth_fwd(const float* verts, int N, int V, int hand_nb, float* unit_gra
 /* reference homan/lossutils.py:39-40 and :107-109: out3 = {mean(pca^2), (s_obj-m_obj)^2, (s_hand-m_hand)^2} */
 int hm_priors_fwd(const float* pca, long npca, const float* s_obj, const float* m_obj, const float* s_hand,
                   const float* m_hand, float* g_pca, float* g_sobj, float* g_shand, float* out3, hipStream_t stream);
-/* hm_v2d_fwd + hm_smooth_fwd (+ hm_priors_fwd when pca != NULL) of the hand vertices in ONE launch (same outputs) */
-int hm_hand_terms_fwd(const float* verts, const float* camintr, int hand_nb, const float* ref2d, float image_size, int N,
-                      int V, float* unit_v2d, float* out_v2d2, float* unit_smooth, float* out_smooth1, const float* pca,
-                      long npca, const float* s_obj, const float* m_obj, const float* s_hand, const float* m_hand,
-                      float* g_pca, float* g_sobj, float* g_shand, float* out_priors3, void* workspace, hipStream_t stream);
 /* reference homan/losses.py:199-242 ('centroid') with the gating of :98-139 (project_bbox :20-49, compute_iou
  * utils/bbox.py:111-135, compute_dist_z utils/geometry.py:69-86).  out1 = un-normalised sum; frame_rec (B,8). */
 int hm_inter_fwd(const float* verts_hand, const float* verts_obj, const float* camintr, int B, int Vh, int Vo,
@@ -447,9 +433,6 @@ int hm_adam_step(const void* slots, int n_tensors, int* step, float beta1, float
 int hm_adam_step_log(const void* slots, int n_tensors, int* step, float beta1, float beta2, float eps, int zero_grad,
                      int blocks_per_tensor, float* vals, const float* weights, int n, int max_steps, float* log, int nclips,
                      hipStream_t stream);
-/* vals[n] = sum_i weights[i]*vals[i] (the weighted total of jointopt.py:180-188), then log row step[0] = vals[0..n] */
-int hm_log_total(float* vals, const float* weights, int n, const int* step, int max_steps, float* log,
-                 hipStream_t stream);
 /* log[step[0]*n + i] = src[i] */
 int hm_log_scalars(const float* src, int n, const int* step, int max_steps, float* log, hipStream_t stream);
 
@@ -540,13 +523,13 @@ int hm_sil_reduce_clips(int B, int V, int F, int S, const float* keep_sum, float
                         void* workspace, int clip_len, int out_stride, hipStream_t stream);
 int hm_sil_bwd_clips(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                      const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-                     const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+                     const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                      int clip_len, float* loss_out, int out_stride, int sum_log2q, hipStream_t stream);
 /* The same backward in two calls (phases: bit 0 = masks + line expansion + work list, bit 1 = edge sweeps + vertex gather; 3 =
  * hm_sil_bwd_clips), for a caller whose other streams wait for the END of the line expansion. */
 int hm_sil_bwd_phase_clips(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                      const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
-                     const int* adj_items, const int* face_order, float* grad_verts, float* grad_ndc, void* workspace,
+                     const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
                      int clip_len, float* loss_out, int out_stride, int phases, int sum_log2q, hipStream_t stream);
 /*   loss_out (optional, modes 1 / 2): the loss / IoU reduction of hm_sil_reduce_clips (same arithmetic) done by extra
  *   workgroups at the front of the backward's first launch, for a forward that was called with loss_out == NULL: the value
@@ -560,6 +543,7 @@ int hm_smooth_fwd_clips(const float* verts, int N, int V, int hand_nb, float* un
 int hm_priors_fwd_clips(const float* pca, long npca, const float* s_obj, const float* m_obj, const float* s_hand,
                         const float* m_hand, float* g_pca, float* g_sobj, float* g_shand, float* out3, int nclips,
                         int out_stride, hipStream_t stream);
+/* hm_v2d_fwd + hm_smooth_fwd (+ hm_priors_fwd when pca != NULL) of the hand vertices in ONE launch (same outputs) */
 int hm_hand_terms_fwd_clips(const float* verts, const float* camintr, int hand_nb, const float* ref2d, float image_size,
                             int N, int V, float* unit_v2d, float* out_v2d2, float* unit_smooth, float* out_smooth1,
                             const float* pca, long npca, const float* s_obj, const float* m_obj, const float* s_hand,
@@ -621,14 +605,9 @@ int hm_log_total_clips(float* vals, const float* weights, int n, const int* step
  * `stream`; avg_ms[0..2] (HOST pointer) receive the average launch durations in milliseconds. */
 int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, int B, int V, int F, int S,
                          const float* keep, const float* ref, const float* keep_sum, float* pooled, float* loss_out,
-                         const int* work_order, const int* adj_off, const int* adj_items, const int* face_order,
+                         const int* work_order, const int* adj_off, const int* adj_items,
                          const float* upstream, float* grad_verts, void* workspace, int reps, float* avg_ms,
                          hipStream_t stream);
-/* hm_debug_sil_timing(1): from then on hm_sil_fwd / hm_sil_bwd record HIP events on their launch stream right before and
- * after k_raster_fwd, k_bwd_lines and k_bwd_sweep, so a caller that issues the optimisation loop launch by launch (not from
- * a captured graph) measures the duration each kernel has inside the loop, next to the work of the other streams;
- * hm_debug_sil_timing_read: durations in ms of the last timed launches {raster, lines, sweep} -> HOST float[3] (waits).
- * Process-wide; hm_debug_sil_timing(0) releases the events. */
 /* In-graph timing of k_raster_fwd / k_bwd_lines / k_bwd_sweep: every workgroup (every wave of the persistent sweep kernel)
  * stores the device wall clock (s_memrealtime) at entry and exit into a slot pair of its own inside the silhouette workspace
  * - for launches replayed from a captured hipGraph, where ROCm allows no events.  B, V, F, S as given to
@@ -640,10 +619,6 @@ size_t hm_sil_timestamps_bytes(int B, int V, int F, int S);
 int hm_sil_timestamps(void* workspace, int B, int V, int F, int S, int enable, hipStream_t stream);
 int hm_sil_timestamps_save(const void* workspace, int B, int V, int F, int S, void* dst, hipStream_t stream);
 int hm_sil_timestamps_read(const void* workspace, int B, int V, int F, int S, const void* saved, float* us3, hipStream_t stream);
-int hm_debug_sil_timing(int enable);
-int hm_debug_sil_timing_read(float* ms3);
-int hm_debug_occupancy(int* raster_fwd_blocks, int* sweep_blocks);
-int hm_debug_read_partials(const void* workspace, int B, int V, int F, int S, float* out, hipStream_t stream);
 
 #ifdef __cplusplus
 }

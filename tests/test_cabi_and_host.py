@@ -55,14 +55,15 @@ def test_ctypes_table_matches_header():
     for entry points that cover every type and shape the header uses, and against an arity counted by this file's own regex."""
     from homan_amd import lib
     VP, I, F, SZ, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
-    sil_bwd = [VP, VP, I, I, I, I, F, F, I, VP, VP, VP, VP, VP, VP, VP, VP, VP]
+    sil_bwd = [VP, VP, I, I, I, I, F, F, I, VP, VP, VP, VP, VP, VP, VP, VP]
     want = {
         "hm_sil_fwd": (I, [VP, VP, I, VP, I, I, I, I, F, F, F, VP, VP, VP, VP, VP, VP, VP, VP, I, VP, VP, VP, I, I, VP, VP]),
         "hm_sil_bwd_phase_clips": (I, sil_bwd + [I, VP, I, I, I, VP]),
         "hm_pair_terms_fwd_clips": (I, [VP, VP, VP, I, I, I, VP, VP, VP, F, F, VP, VP, VP, VP, VP, VP,
                                         VP, F, VP, VP, VP, VP, VP, L, VP, VP, VP, VP, VP, VP, VP, VP, VP,
                                         VP, VP, VP, VP, VP, VP, VP, VP, I, I, VP]),
-        "hm_lincomb4": (I, [VP, F, VP, F, VP, F, VP, F, L, VP, VP]),
+        "hm_hand_terms_fwd_clips": (I, [VP, VP, I, VP, F, I, I, VP, VP, VP, VP, VP, L, VP, VP, VP, VP, VP, VP, VP, VP, VP, I, I, VP]),
+        "hm_scale_by": (I, [VP, VP, L, VP, VP]),
         "hm_priors_fwd": (I, [VP, L, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
         "hm_sil_workspace_bytes": (SZ, [I, I, I, I]),
         "hm_sil_parts": (VP, [VP, I, I, I, I]),

@@ -181,7 +181,7 @@ def test_persistent_outputs_skip_is_invisible():
         one = torch.ones(1, device=dev)
         for sc, g in ((sp, gp), (sf, gf)):
             hlib.check(L.hm_sil_bwd(P(v), P(Kd), B, V, F, S, 1.0, 1e-3, 1, P(one), None, P(ksd), P(sc.adj_off),
-                                    P(sc.adj_items), None, P(g), None, P(sc.workspace), 0, hlib.stream()), "hm_sil_bwd")
+                                    P(sc.adj_items), P(g), None, P(sc.workspace), 0, hlib.stream()), "hm_sil_bwd")
         assert torch.equal(gp, gf), step
 
 
@@ -391,7 +391,7 @@ def test_multi_render_launch_equals_separate_calls(B, S):
     for ctxs, out in ((c_a, o_a), (c_b, o_b)):
         gv = torch.empty(B, Vo, 3, device=dev)
         ck(L.hm_sil_bwd_clips(P(out[5]), P(sc["K_roi"]), B, Vo, Fo, S, 1.0, ops.NMR_EPS, 2, P(up), None, P(keep_sum),
-                              P(ctxs[0].adj_off), P(ctxs[0].adj_items), None, P(gv), None, P(ctxs[0].workspace), B, None, 0, 0,
+                              P(ctxs[0].adj_off), P(ctxs[0].adj_items), P(gv), None, P(ctxs[0].workspace), B, None, 0, 0,
                               stream), "hm_sil_bwd_clips")
         gd_o, gd_c = torch.empty(B, Vo, 3, device=dev), torch.empty(B, Vc, 3, device=dev)
         ck(L.hm_depth_bwd(P(out[5]), P(sc["K_full"]), B, Vo, Fo, S, 1.0, P(g_depth), P(ctxs[1].adj_off), P(ctxs[1].adj_items),
@@ -456,3 +456,55 @@ def test_multi_render_launch_one_and_four_renders(n):
     for (ca, pa, da), (cb, pb, db) in zip(single, multi):
         assert torch.equal(pa, pb) and torch.equal(da, db) and torch.equal(ca.idx_map(), cb.idx_map())
         assert float(pa.sum()) > 1.0
+
+
+def test_context_launch_methods_equal_raw_calls():
+    """SilhouetteContext.forward / backward (keywords) = the raw hm_sil_fwd_clips / hm_sil_bwd_clips calls written out positionally,
+    bit for bit, on a call that uses most of the surface: two clips of two frames, the rigid transform in the face setup with the
+    camera-space vertices written out, keep / ref, persistent outputs, the forward in its two phases, the loss / IoU reduction in
+    front of the backward with an output stride.  Cube (V = 8, F = 12) at S = 32, the smallest size the backward takes."""
+    from homan_amd import lib as hlib
+    from homan_amd import ops, synth
+    B, CL, S, NS = 4, 2, 32, 5
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(11)
+    cv, cf = synth.box_mesh(1, 1, 1)
+    V, F = cv.shape[0], cf.shape[0]
+    assert (V, F) == (8, 12)
+    mesh = torch.from_numpy(cv)[None].repeat(B, 1, 1).float().contiguous().to(dev)
+    faces = torch.from_numpy(cf).int()[None].expand(B, -1, -1).to(dev)
+    rot = torch.randn(B, 3, 2, generator=g).to(dev)
+    trans = (torch.tensor([[0.0, 0.0, 0.6]]) + torch.randn(B, 3, generator=g) * 0.01).to(dev)
+    scale = torch.tensor([1.1, -0.9]).to(dev)                       # one per clip; rigid_abs takes |s|
+    K = torch.tensor([[2.6, 0, 0.5], [0, 2.6, 0.5], [0, 0, 1.0]]).repeat(B, 1, 1).to(dev)
+    keep = (torch.rand(B, S, S, generator=g) > 0.2).float().to(dev)
+    ref = ((torch.rand(B, S, S, generator=g) > 0.5).float().to(dev) * keep).contiguous()
+    keep_sum = keep.reshape(B // CL, -1).sum(1).contiguous()
+    up = torch.ones(1, device=dev)
+    L, P, ck, stream = hlib.lib(), hlib.ptr, hlib.check, hlib.stream()
+
+    def state():
+        return (ops.SilhouetteContext(faces, V, B, S, dev), torch.full((B, S, S), -7.0, device=dev),
+                torch.full((B, V, 3), -7.0, device=dev), torch.full((B // CL, NS), -7.0, device=dev))
+
+    # ---- A: the methods
+    ca, pooled_a, vo_a, loss_a = state()
+    fwd = dict(verts=mesh, K=K, keep=keep, ref=ref, pooled=pooled_a, rigid_rot6d=rot, rigid_trans=trans, rigid_scale=scale,
+               rigid_abs=1, cam_verts_out=vo_a, persistent_outputs=1, clip_len=CL, out_stride=NS)
+    ck(ca.forward(phases=1, **fwd), "forward(setup)")
+    ck(ca.forward(phases=2, **fwd), "forward(raster)")
+    ck(ca.backward(vo_a, K, 2, upstream=up, keep_sum=keep_sum, loss_out=loss_a, clip_len=CL, out_stride=NS), "backward")
+    # ---- B: the raw entry points
+    cb, pooled_b, vo_b, loss_b = state()
+    ck(L.hm_sil_fwd_clips(P(mesh), P(cb.faces), 0, P(K), B, V, F, S, 1.0, ops.NMR_NEAR, ops.NMR_FAR, P(keep), P(ref), None, P(pooled_b),
+                          None, P(cb.work_order), None, None, 0, P(rot), P(trans), P(scale), 1, 1, P(cb.workspace), CL, NS, P(vo_b),
+                          stream), "hm_sil_fwd_clips")
+    ck(L.hm_sil_bwd_clips(P(vo_b), P(K), B, V, F, S, 1.0, ops.NMR_EPS, 2, P(up), None, P(keep_sum), P(cb.adj_off), P(cb.adj_items),
+                          None, None, P(cb.workspace), CL, P(loss_b), NS, 0, stream), "hm_sil_bwd_clips")
+    torch.cuda.synchronize()
+    assert torch.equal(pooled_a, pooled_b) and torch.equal(vo_a, vo_b)
+    assert torch.equal(ca.idx_map(), cb.idx_map()) and torch.equal(ca.parts(), cb.parts())
+    assert torch.equal(loss_a, loss_b)
+    # ... and the call did something: coverage, gradients, both clips' loss / IoU slots written and nothing beside them
+    assert float(pooled_a.clamp_min(0).sum()) > 10 and float(ca.parts().abs().sum()) > 0 and float((vo_a[..., 2] - 0.6).abs().max()) < 0.2
+    assert bool((loss_a[:, :2] != -7).all()) and bool((loss_a[:, 2:] == -7).all()) and bool(torch.isfinite(loss_a).all())

@@ -55,7 +55,7 @@ def main():
     hlib.check(hlib.lib().hm_bench_sil_kernels(
         hlib.ptr(verts), hlib.ptr(sctx.faces), hlib.ptr(m.camintr_rois_object), B, V, F, S, hlib.ptr(m.keep_mask_object),
         hlib.ptr(m.ref_mask_object), hlib.ptr(ksum), hlib.ptr(pooled), hlib.ptr(out2), hlib.ptr(sctx.work_order),
-        hlib.ptr(sctx.adj_off), hlib.ptr(sctx.adj_items), None, hlib.ptr(one), hlib.ptr(gv), hlib.ptr(sctx.workspace),
+        hlib.ptr(sctx.adj_off), hlib.ptr(sctx.adj_items), hlib.ptr(one), hlib.ptr(gv), hlib.ptr(sctx.workspace),
         args.reps, ms.data_ptr(), hlib.stream()), "hm_bench_sil_kernels")
     chain = None
     if args.chain:

@@ -100,12 +100,12 @@ def main():
     reps = 200
     for _ in range(2):       # (the first series warms up; a series of 200 launches is 10-60 ms per kernel: ten of them below)
         hlib.check(L.hm_bench_sil_kernels(P(verts), P(hard.faces), P(K), B, V, F, S, P(keep), P(ref), P(model.losses.keep_sum),
-                                          P(pooled), P(out2), P(hard.work_order), P(hard.adj_off), P(hard.adj_items), None, P(one),
+                                          P(pooled), P(out2), P(hard.work_order), P(hard.adj_off), P(hard.adj_items), P(one),
                                           P(gverts), P(hard.workspace), reps, ms.data_ptr(), hlib.stream()), "hm_bench_sil_kernels")
     acc, series = [0.0, 0.0, 0.0], 10
     for _ in range(series):
         hlib.check(L.hm_bench_sil_kernels(P(verts), P(hard.faces), P(K), B, V, F, S, P(keep), P(ref), P(model.losses.keep_sum),
-                                          P(pooled), P(out2), P(hard.work_order), P(hard.adj_off), P(hard.adj_items), None, P(one),
+                                          P(pooled), P(out2), P(hard.work_order), P(hard.adj_off), P(hard.adj_items), P(one),
                                           P(gverts), P(hard.workspace), reps, ms.data_ptr(), hlib.stream()), "hm_bench_sil_kernels")
         acc = [x + float(y) for x, y in zip(acc, ms)]
     r, sw, ln = (x / series for x in acc)
