@@ -395,6 +395,44 @@ def soft_silhouette_render(verts, K, sctx, sigma, orig_size=1.0):
     return _SoftSilhouetteRender.apply(verts, K, sctx, sigma, orig_size)
 
 
+def softsil_pose_workspace(n, size, device):
+    """zero-filled ticket / partials buffer of hm_softsil_pose_terms for n candidates at mask size `size`"""
+    nbytes = _lib.lib().hm_softsil_pose_workspace_bytes(int(n), int(size))
+    if nbytes == 0:
+        raise _lib.HomanAmdError(f"soft pose terms: unsupported shape N={n} S={size}")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+class _SoftSilPoseTerms(torch.autograd.Function):
+    """The masked L2 and the IoU of the pose initialisation on the soft image (csrc/softpose.hip, hm_softsil_pose_terms): the
+    expressions of reference homan/pose_optimization.py:138-147 on image = keep * alpha, one shared mask for every candidate."""
+
+    @staticmethod
+    def forward(ctx, alpha, keep, ref, workspace):
+        alpha = _f32(alpha).contiguous()
+        n, size = alpha.shape[0], alpha.shape[1]
+        assert alpha.shape == (n, size, size) and keep.shape == (size, size) and ref.shape == (size, size)
+        terms = torch.empty(n, 2, device=alpha.device)
+        grad = torch.empty_like(alpha)
+        _lib.check(_lib.lib().hm_softsil_pose_terms(_lib.ptr(alpha), _lib.ptr(keep), _lib.ptr(ref), n, size, _lib.ptr(terms),
+                                                    _lib.ptr(grad), _lib.ptr(workspace), _lib.stream()), "hm_softsil_pose_terms")
+        ctx.save_for_backward(grad)
+        mask, iou = terms[:, 0], terms[:, 1]
+        ctx.mark_non_differentiable(iou)
+        return mask, iou
+
+    @staticmethod
+    def backward(ctx, g_mask, _g_iou):
+        grad, = ctx.saved_tensors
+        return _f32(g_mask)[:, None, None] * grad, None, None, None
+
+
+def softsil_pose_terms(alpha, keep, ref, workspace):
+    """alpha (n,S,S) soft images, keep / ref (S,S) 0 / 1 -> (per-candidate sum of squares (n,), per-candidate IoU (n,) [no
+    gradient]); workspace: softsil_pose_workspace(n, S, device)."""
+    return _SoftSilPoseTerms.apply(alpha, keep, ref, workspace)
+
+
 class _DepthRender(torch.autograd.Function):
     """reference homan/homan.py:391,406: `_, depths, sils = renderer.render(verts, faces, textures, K=)`.
     -> (silhouettes (B,S,S), depths (B,S,S)); only the depth image is differentiable here (the ordinal depth loss uses

@@ -83,19 +83,57 @@ def TCO_init_from_boxes_zup_autodepth(boxes_2d, model_points_3d, K):
     return torch.cat([xy, depth], 1)
 
 
+def _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer=0):
+    """The silhouette-mode keywords of PoseOptimizer / PoseFitter / find_optimal_pose(s), checked on the host before any device
+    work -> (sigma, decay, floor) as floats, floor 0.0 for `sil_sigma_min=None` (nothing is read of them in mode "nmr")."""
+    if sil_mode not in ("nmr", "soft"):
+        raise ValueError(f"sil_mode {sil_mode!r} not in ('nmr', 'soft')")
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+    if not (number(sil_sigma) and sil_sigma > 0):
+        raise ValueError(f"sil_sigma must be a positive finite number, got {sil_sigma!r}")
+    if not (number(sil_sigma_decay) and 0 < sil_sigma_decay <= 1):
+        raise ValueError(f"sil_sigma_decay must lie in (0, 1], got {sil_sigma_decay!r}")
+    if sil_sigma_min is not None and not (number(sil_sigma_min) and 0 < sil_sigma_min <= sil_sigma):
+        raise ValueError(f"sil_sigma_min must lie in (0, sil_sigma], got {sil_sigma_min!r}")
+    if sil_mode == "soft" and lw_chamfer != 0:
+        raise NotImplementedError("sil_mode='soft' has no edge-chamfer term (the edge band of a blurred image is not defined): "
+                                  "lw_chamfer must be 0")
+    return float(sil_sigma), float(sil_sigma_decay), float(sil_sigma_min or 0.0)
+
+
+def _sil_extra(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min):
+    """what a soft fit adds to a fitter's positional arguments and to its key; nothing in mode "nmr" (one fitter whatever the unused
+    soft keywords say)"""
+    if sil_mode == "nmr":
+        return ()
+    return (sil_mode, float(sil_sigma), float(sil_sigma_decay), None if sil_sigma_min is None else float(sil_sigma_min))
+
+
 class PoseOptimizer(nn.Module):
     """reference homan/pose_optimization.py:37-160 (occlusion-aware silhouette loss + one-way edge chamfer + off-screen
-    penalty over `num_initializations` candidate poses of one mesh against one instance mask)."""
+    penalty over `num_initializations` candidate poses of one mesh against one instance mask).
+
+    sil_mode="soft" (a non-parity extra, no reference counterpart): the image is the Soft Rasterizer silhouette of
+    csrc/softsil.hip at the mask's own resolution - any size from 1 to 4096, odd ones included -, blur `sil_sigma` (NDC^2), with
+    a true gradient, depth included; mask loss and IoU are the same expressions on image = keep * alpha
+    (hm_softsil_pose_terms), `lw_chamfer` must be 0.  `self.sil_sigma` is the 1-element device tensor the kernels read when they
+    run; `anneal()` - called by every loop after its optimiser step - is sigma <- max(sigma * sil_sigma_decay, sil_sigma_min
+    or 0) in float32.  A fit starts from `sil_sigma`, and the module it returns holds the sigma it ENDED with.  With a decay the
+    best-ever rule of the loops compares losses taken at different blurs - a sharper image of a well-placed pose has the smaller
+    loss - and so favours late steps."""
 
     def __init__(self, ref_image, vertices, faces, rotation_init, translation_init, num_initializations=1, kernel_size=7,
-                 K=None, power=0.25, lw_chamfer=0, textures=None, _shared=None):
+                 K=None, power=0.25, lw_chamfer=0, textures=None, _shared=None, sil_mode="nmr", sil_sigma=1e-4,
+                 sil_sigma_decay=1.0, sil_sigma_min=None):
         assert ref_image.shape[0] == ref_image.shape[1], "Must be square."
         super().__init__()
+        sigma0, decay, floor = _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer)
         if not torch.cuda.is_available():
             raise RuntimeError("homan_amd.pose_optimization needs an MI355X (ROCm) device; there is no CPU path")
         dev = torch.device("cuda")
         size = int(ref_image.shape[0])
-        if size % 2:
+        self.sil_mode, self._sigma0, self._sigma_decay, self._sigma_floor = sil_mode, sigma0, decay, floor
+        if sil_mode == "nmr" and size % 2:
             raise NotImplementedError(f"pose initialisation renders on a grid of 2x2-sample pixels: even mask sizes only "
                                       f"(the reference's REND_SIZE is 256), got {size}")
         # (sizes off the kernels' 64-sample tile grid are rendered on the next one and cropped: ops.SilhouetteContext)
@@ -130,10 +168,19 @@ class PoseOptimizer(nn.Module):
         self.image_size, self.lw_chamfer = size, lw_chamfer
         self.to(dev)
         self._K_all = self.K.repeat(n, 1, 1).contiguous()
+        if sil_mode == "soft":
+            # (own to every module, never shared: a fit's result keeps the blur it ended with)
+            self.sil_sigma = torch.full((1,), sigma0, dtype=torch.float32, device=dev)
         if _shared is not None:
             self._one, self._sil_ctx = _shared._one, _shared._sil_ctx
+            self._pose_ws = _shared._pose_ws
+        elif sil_mode == "soft":
+            self._one = torch.ones(1, device=dev)
+            self._sil_ctx = ops.SoftSilhouetteContext(self.faces, self.vertices.shape[1], n, size, dev)
+            self._pose_ws = ops.softsil_pose_workspace(n, size, dev)
         else:
             self._one = torch.ones(1, device=dev)
+            self._pose_ws = None
             self._sil_ctx = ops.SilhouetteContext(self.faces, self.vertices.shape[1], n, size // 2, dev)
             # the masked L2 of :138-143 is an unnormalised sum of squares: per-sample gradients are O(1), pseudo-gradient terms
             # up to 2 / eps, per-frame sums up to ~1e7 - the order-independent sums of the backward run on the grid 2^-24 (exact
@@ -176,10 +223,29 @@ class PoseOptimizer(nn.Module):
     def compute_edges(self, silhouette):
         return self.pool(silhouette) - silhouette
 
+    def anneal(self):
+        """one step of the blur schedule, sigma <- max(sigma * decay, floor) in float32 (the arithmetic of hm_sigma_anneal), in
+        place and capturable; nothing in mode "nmr" or with decay 1"""
+        if self.sil_mode == "soft" and self._sigma_decay < 1.0:
+            with torch.no_grad():
+                self.sil_sigma.mul_(self._sigma_decay).clamp_(min=self._sigma_floor)
+
+    def reset_sigma(self):
+        """the blur a fit starts from"""
+        if self.sil_mode == "soft":
+            self.sil_sigma.fill_(self._sigma0)
+
     def forward(self):
         verts = self.apply_transformation()
         loss_dict = {}
-        if self.lw_chamfer == 0:
+        if self.sil_mode == "soft":
+            alpha = ops.soft_silhouette_render(verts, self._K_all, self._sil_ctx, self.sil_sigma, 1.0)
+            mask_loss, iou = ops.softsil_pose_terms(alpha, self._keep1, self._ref1, self._pose_ws)
+            loss_dict["mask"] = mask_loss
+            iou = iou.detach()
+            image = self.keep_mask * alpha.detach()
+            loss_dict["chamfer"] = torch.zeros_like(mask_loss)
+        elif self.lw_chamfer == 0:
             # render + keep-mask + per-pose L2 + IoU in the rasteriser's epilogue (hm_sil_fwd with a per-sample mask)
             mask_loss, iou, alpha = ops.masked_silhouette_l2_noaa(verts, self._K_all, self._keep1, self._ref1,
                                                                   self._sil_ctx, 1.0)
@@ -217,6 +283,7 @@ def _graph_loop(model, lr, num_iterations):
         losses = sum(loss_dict.values())
         losses.sum().backward()
         optimizer.step()
+        model.anneal()
         with torch.no_grad():
             lmin, ind = losses.min(0)
             better = lmin < best_loss
@@ -312,12 +379,17 @@ class _FusedPoseLoop:
         L, P, ck = _lib.lib(), _lib.ptr, _lib.check
         sctx, dev = model._sil_ctx, model.rotations.device
         n, V, F, S = sctx.B, sctx.V, sctx.F, sctx.S
+        soft = self.soft = model.sil_mode == "soft"
         f = lambda *shape: torch.zeros(*shape, device=dev)
         verts, g_off, off = f(n, V, 3), f(n, V, 3), f(n)
         pooled, frame = f(n, S, S), f(n, 2)
-        # (views of the model's own tensors when the mask size lies on the kernels' tile grid, copies otherwise: refresh())
-        self.keep, self.ref = sctx.pad_samples(model._keep1).contiguous(), sctx.pad_samples(model._ref1).contiguous()
-        self.K_all, self.K_one = sctx.K_eff(model._K_all).contiguous(), model.K[0].contiguous()
+        if soft:
+            # (the soft image has the mask's own size: nothing is padded, the model's tensors are read where they lie)
+            self.keep, self.ref, self.K_all, self.K_one = model._keep1, model._ref1, model._K_all, model.K[0].contiguous()
+        else:
+            # (views of the model's own tensors when the mask size lies on the kernels' tile grid, copies otherwise: refresh())
+            self.keep, self.ref = sctx.pad_samples(model._keep1).contiguous(), sctx.pad_samples(model._ref1).contiguous()
+            self.K_all, self.K_one = sctx.K_eff(model._K_all).contiguous(), model.K[0].contiguous()
         keep, ref, K_all, K_one = self.keep, self.ref, self.K_all, self.K_one
         ones = torch.ones(n, device=dev)
         rws = torch.zeros(L.hm_rigid_workspace_bytes(n), dtype=torch.uint8, device=dev)
@@ -333,6 +405,11 @@ class _FusedPoseLoop:
         self.log_steps = int(log_steps)
         self.log = log = f(self.log_steps, 16) if self.log_steps > 0 else None
         self._keepalive = (verts, g_off, off, pooled, frame, ones, rws, tp, tw)
+        self.edge = None
+        self.graph = None
+        if soft:
+            self._step = self._soft_step(verts, g_off, off, pooled, frame, rws)
+            return
         self.edge = edge = _EdgeTermBuffers(model, self.ref) if model.lw_chamfer != 0 else None
 
         # one binary mask for every candidate and no per-sample outputs (mask_shared = 1 | 2, see include/homan_amd.h) - or, with the
@@ -373,11 +450,57 @@ class _FusedPoseLoop:
         if edge is not None:
             edge.refresh()
 
+    def _soft_step(self, verts, g_off, off, alpha, frame, rws):
+        """The step in mode "soft": rigid transform, off-screen penalty, soft image (hm_softsil_fwd at the mask's size), masked
+        L2 + IoU + the image gradient in one pass (hm_softsil_pose_terms), the soft backward to vertex gradients, the plain
+        rigid backward over {off-screen, silhouette} vertex gradients, Adam, best-ever bookkeeping, and - with a decay - the
+        blur schedule's update (hm_sigma_anneal): sigma lies in the model's `sil_sigma` and is read by the kernels as they run."""
+        model, opt = self.model, self.opt
+        L, P, ck = _lib.lib(), _lib.ptr, _lib.check
+        sctx, dev = model._sil_ctx, model.rotations.device
+        n, V, F, S = sctx.B, sctx.V, sctx.F, sctx.S
+        keep, ref, K_all, K_one, sigma = self.keep, self.ref, self.K_all, self.K_one, model.sil_sigma
+        g_img, g_sil = torch.zeros(n, S, S, device=dev), torch.zeros(n, V, 3, device=dev)
+        pws = ops.softsil_pose_workspace(n, S, dev)
+        tp, tw, tn = _lib.terms([(g_off, 1.0), (g_sil, 1.0)])
+        self._keepalive += (g_img, g_sil, pws, tp, tw)
+        decay, floor = model._sigma_decay, model._sigma_floor
+        log, losses_out = self.log, self.losses_out
+        render = (P(sctx.faces), P(K_all), n, V, F, S, 1.0, ops.NMR_NEAR, ops.NMR_FAR, P(sigma), P(alpha))
+
+        def step():
+            st = _lib.stream()
+            ck(L.hm_rigid_fwd(P(model.vertices), P(model.rotations), P(model.translations), P(model._one), 0, n, V, None, P(verts),
+                              st), "hm_rigid_fwd")
+            ck(L.hm_offscreen_fwd(P(verts), P(K_one), n, V, NMR_FAR, 100000.0, P(off), P(g_off), st), "hm_offscreen_fwd")
+            ck(L.hm_softsil_fwd(P(verts), *render, P(sctx.workspace), st), "hm_softsil_fwd")
+            ck(L.hm_softsil_pose_terms(P(alpha), P(keep), P(ref), n, S, P(frame), P(g_img), P(pws), st), "hm_softsil_pose_terms")
+            ck(L.hm_softsil_bwd(P(verts), *render, P(g_img), P(sctx.adj_off), P(sctx.adj_items), P(g_sil), P(sctx.workspace), st),
+               "hm_softsil_bwd")
+            ck(L.hm_rigid_bwd(P(model.vertices), P(model.rotations), P(model._one), 0, tp, tw, tn, None, None, 0, 0.0, n, V, None,
+                              P(model.rotations.grad), P(model.translations.grad), None, P(rws), st), "hm_rigid_bwd")
+            opt.step(zero_grad=False)
+            if log is not None:
+                ck(L.hm_pose_keep_best_log(P(frame), 2, P(off), n, P(model.rotations), P(model.translations), P(opt.step_t),
+                                           self.log_steps, P(log), P(losses_out), st), "hm_pose_keep_best_log")
+            else:
+                ck(L.hm_pose_keep_best(P(frame), 2, P(off), n, P(model.rotations), P(model.translations), P(self.best_loss),
+                                       P(self.best_rot), P(self.best_trans), P(losses_out), st), "hm_pose_keep_best")
+            if decay < 1.0:
+                ck(L.hm_sigma_anneal(P(sigma), decay, floor, st), "hm_sigma_anneal")
+
+        return step
+
     def restart(self):
         """a new fit in the bound model's tensors: derived inputs refreshed, optimiser and best-ever state as new"""
         m, sctx = self.model, self.model._sil_ctx
-        for dst, src in ((self.keep, sctx.pad_samples(m._keep1)), (self.ref, sctx.pad_samples(m._ref1)),
-                         (self.K_all, sctx.K_eff(m._K_all)), (self.K_one, m.K[0])):
+        if self.soft:
+            m.reset_sigma()
+            pairs = ((self.K_one, m.K[0]),)
+        else:
+            pairs = ((self.keep, sctx.pad_samples(m._keep1)), (self.ref, sctx.pad_samples(m._ref1)),
+                     (self.K_all, sctx.K_eff(m._K_all)), (self.K_one, m.K[0]))
+        for dst, src in pairs:
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         for mm, vv in self.opt.state:
@@ -420,7 +543,10 @@ class _FusedPoseLoop:
 
     def stamped_replays(self, stamp_reps):
         """(bench.py) `stamp_reps` MORE replays with the heavy silhouette kernels stamping the device wall clock
-        (hm_sil_timestamps) -> their average durations in microseconds (raster, lines, sweep)"""
+        (hm_sil_timestamps) -> their average durations in microseconds (raster, lines, sweep); hard-path instrumentation:
+        None in soft mode"""
+        if self.soft:
+            return None
         import ctypes
         L, P, ck = _lib.lib(), _lib.ptr, _lib.check
         sctx = self.model._sil_ctx
@@ -470,9 +596,14 @@ class PoseFitter:
     all candidates, strict `<` - is applied over the groups' records after the last step: the same champion, the same poses and
     losses as one loop over all candidates, bit for bit (tests/test_poseinit.py)."""
 
-    def __init__(self, vertices, faces, num_initializations, size, lr, lw_chamfer=0, kernel_size=7, power=0.25):
+    def __init__(self, vertices, faces, num_initializations, size, lr, lw_chamfer=0, kernel_size=7, power=0.25,
+                 sil_mode="nmr", sil_sigma=1e-4, sil_sigma_decay=1.0, sil_sigma_min=None):
         n = num_initializations
+        _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer)
         self.term_kw = dict(lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)      # (the edge-chamfer term, :145-147)
+        if sil_mode != "nmr":
+            # (mode "soft": each group's shell owns its sigma tensor; the groups run the same schedule and end at the same value)
+            self.term_kw.update(sil_mode=sil_mode, sil_sigma=sil_sigma, sil_sigma_decay=sil_sigma_decay, sil_sigma_min=sil_sigma_min)
         # (same-box bench.py --pose-init N, pose-steps/s with 1 / 2 / 3 / 4 groups: N = 128: 312 k / 354 k / 371 k; 250: 410 k / 420 k /
         #  467 k; 500: 476 k / 533 k / 565 k / 517 k; 2000: 502 k / 574 k / 585 k)
         parts = int(os.environ.get("HOMAN_POSE_PARTS", "0")) or (3 if n >= 96 else 2 if n >= 48 else 1)
@@ -568,6 +699,8 @@ class PoseFitter:
             for (lo, hi), sh in zip(zip(self.cuts[:-1], self.cuts[1:]), self.shells):
                 result.rotations[lo:hi].copy_(sh.rotations)
                 result.translations[lo:hi].copy_(sh.translations)
+            if result.sil_mode == "soft":
+                result.sil_sigma.copy_(self.shells[0].sil_sigma)          # (the blur the fit ended with)
         losses = torch.cat([lp.losses_out for lp in loops])
         self.fits += 1
         return result, losses, champ_rot, champ_trans
@@ -588,6 +721,8 @@ class PoseFitter:
         with torch.no_grad():
             result.rotations.copy_(sh.rotations)
             result.translations.copy_(sh.translations)
+            if result.sil_mode == "soft":
+                result.sil_sigma.copy_(sh.sil_sigma)                      # (the blur the fit ended with)
         self.fits += 1
         return result, losses.clone(), champ_rot, champ_trans
 
@@ -618,18 +753,21 @@ def _digest(t):
     return hash((tuple(t.shape), str(t.dtype), t.detach().cpu().contiguous().numpy().tobytes()))
 
 
-def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None, lw_chamfer=0, kernel_size=7, power=0.25):
+def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None, lw_chamfer=0, kernel_size=7, power=0.25, sil_mode="nmr",
+                     sil_sigma=1e-4, sil_sigma_decay=1.0, sil_sigma_min=None):
     import os
     if os.environ.get("HOMAN_POSE_FITTER", "1") == "0":
         return None
+    _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer)
+    sil = _sil_extra(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min)
     mesh_key = mesh_key or (_digest(vertices), _digest(faces))
     key = (*mesh_key, tuple(vertices.shape), tuple(faces.shape), int(n), int(size), float(lr), float(lw_chamfer),
-           int(kernel_size), float(power))
+           int(kernel_size), float(power), *sil)
     fitter = _FITTERS.get(key)
     if fitter is None:
         while len(_FITTERS) >= _fitters_max():
             _FITTERS.popitem(last=False)              # least recently used
-        fitter = _FITTERS[key] = PoseFitter(vertices, faces, n, size, lr, lw_chamfer, kernel_size, power)
+        fitter = _FITTERS[key] = PoseFitter(vertices, faces, n, size, lr, lw_chamfer, kernel_size, power, *sil)
     else:
         _FITTERS.move_to_end(key)
     return fitter
@@ -638,7 +776,8 @@ def _resident_fitter(vertices, faces, n, size, lr, mesh_key=None, lw_chamfer=0, 
 def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=None, num_iterations=50,
                       num_initializations=2000, lr=1e-2, image=None, debug=False, viz_folder="tmp", viz_step=10,
                       sort_best=True, rotations_init=None, viz=False, rend_size=constants.REND_SIZE, mode="auto",
-                      lw_chamfer=0, kernel_size=7, power=0.25):
+                      lw_chamfer=0, kernel_size=7, power=0.25, sil_mode="nmr", sil_sigma=1e-4, sil_sigma_decay=1.0,
+                      sil_sigma_min=None):
     """reference homan/pose_optimization.py:219-383 (debug plots not provided: `debug` / `viz` / `image` are accepted
     and ignored).  Returns the PoseOptimizer whose `rotations` / `translations` hold the best-ever pose first, then the
     poses sorted by final loss.
@@ -648,7 +787,12 @@ def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=No
     (`_FusedPoseLoop`), run by a resident `PoseFitter` kept per (mesh, candidates, mask size, lr) - HOMAN_POSE_FITTER=0
     builds everything anew per call;
     mode="eager": the reference loop verbatim (torch autograd + Adam, one host sync per step for the best-ever bookkeeping);
-    mode="graph": that same autograd step captured once in a hipGraph and replayed."""
+    mode="graph": that same autograd step captured once in a hipGraph and replayed.
+    sil_mode="soft" (+ sil_sigma, sil_sigma_decay, sil_sigma_min; PoseOptimizer's keywords): the Soft Rasterizer image with a true
+    gradient and an annealed blur instead of the hard rasteriser's, in every mode, at any mask size from 1 to 4096; the returned
+    module holds the blur the fit ended with.  A non-parity extra: the reference has no counterpart."""
+    _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer)
+    sil_kw = dict(sil_mode=sil_mode, sil_sigma=sil_sigma, sil_sigma_decay=sil_sigma_decay, sil_sigma_min=sil_sigma_min)
     dev = torch.device("cuda")
     mesh_key = ((_digest(vertices), _digest(faces)) if torch.is_tensor(vertices) and torch.is_tensor(faces) else None)     # (the caller's tensors, before the device copies below)
     vertices = torch.as_tensor(vertices).float().to(dev)
@@ -668,9 +812,9 @@ def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=No
     if mode not in ("eager", "graph", "fused"):
         raise ValueError(f"mode {mode} not in [auto|fused|eager|graph]")
     fitter = None
-    if mode == "fused" and num_iterations > 0 and np.asarray(mask).shape[0] % 2 == 0:
+    if mode == "fused" and num_iterations > 0 and (sil_mode == "soft" or np.asarray(mask).shape[0] % 2 == 0):
         fitter = _resident_fitter(vertices, faces, num_initializations, int(np.asarray(mask).shape[0]), lr, mesh_key,
-                                  lw_chamfer, kernel_size, power)
+                                  lw_chamfer, kernel_size, power, **sil_kw)
     if fitter is not None:
         model, final_losses, champion_rot, champion_trans = fitter.fit(mask, matrix_to_rot6d(rotations_init), translations_init,
                                                                        camintr_roi, num_iterations)
@@ -678,7 +822,7 @@ def find_optimal_pose(vertices, faces, mask, bbox, square_bbox, image_size, K=No
         return model
     model = PoseOptimizer(ref_image=mask, vertices=vertices, faces=faces, rotation_init=matrix_to_rot6d(rotations_init),
                           translation_init=translations_init, num_initializations=num_initializations, K=camintr_roi,
-                          lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)
+                          lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power, **sil_kw)
     if mode == "fused" and num_iterations > 0:
         final_losses, champion_rot, champion_trans = _fused_loop(model, lr, num_iterations)
     elif mode == "graph" and num_iterations > 0:
@@ -702,6 +846,7 @@ def _host_loop(model, lr, num_iterations):
         per_pose = sum(terms.values())
         per_pose.sum().backward()
         adam.step()
+        model.anneal()
         value, where = per_pose.detach().min(0)
         if float(value) < champion["loss"]:
             champion = dict(loss=float(value), rot=model.rotations.detach()[where].clone(),
@@ -735,13 +880,17 @@ def rot6d_to_matrix(rot_6d):
 
 def find_optimal_poses(image_size, faces=None, vertices=None, annotations=None, images=None, Ks=None, num_iterations=50,
                        num_initializations=2000, viz_path="tmp.png", debug=False, rend_size=constants.REND_SIZE,
-                       mode="auto", lw_chamfer=0, kernel_size=7, power=0.25):
+                       mode="auto", lw_chamfer=0, kernel_size=7, power=0.25, sil_mode="nmr", sil_sigma=1e-4,
+                       sil_sigma_decay=1.0, sil_sigma_min=None):
     """reference homan/pose_optimization.py:386-488 - the entry point of fit_vid_dataset.py:285-296.  One
     `find_optimal_pose` fit per frame, every frame started from the previous frame's `num_initializations` rotations
     (`sort_best=False` keeps the candidates aligned across frames); the motion kept is the candidate with the highest mean
     IoU over the clip (:468).  annotations[i]: {"target_crop_mask" (S,S) ndarray in {-1,0,1}, "bbox" xywh, "square_bbox"
     xywh, "full_mask" tensor}.  Returns one dict per frame: rotations (1,3,3), translations (1,1,3), verts_trans (1,V,3),
-    target_masks (1,S,S), K_roi (1,1,3,3), masks, verts (1,V,3), full_mask."""
+    target_masks (1,S,S), K_roi (1,1,3,3), masks, verts (1,V,3), full_mask.
+    sil_mode / sil_sigma / sil_sigma_decay / sil_sigma_min: find_optimal_pose's; in mode "soft" the IoU that picks the clip's
+    candidate is taken on the soft image at the blur each frame's fit ended with."""
+    _check_sil_options(sil_mode, sil_sigma, sil_sigma_decay, sil_sigma_min, lw_chamfer)
     mesh_v, mesh_f = torch.as_tensor(vertices), torch.as_tensor(faces)
     if mesh_v.dim() != 2 or mesh_v.shape[1] != 3 or mesh_f.dim() != 2 or mesh_f.shape[1] != 3:
         raise AssertionError("vertices (V,3) and faces (F,3) of ONE mesh expected")
@@ -758,7 +907,8 @@ def find_optimal_poses(image_size, faces=None, vertices=None, annotations=None, 
                                 bbox=ann["bbox"], square_bbox=ann["square_bbox"], image_size=image_size, K=Ks[t],
                                 num_iterations=num_iterations, num_initializations=num_initializations, debug=debug,
                                 sort_best=False, rotations_init=seed_rotations, rend_size=rend_size, mode=mode,
-                                lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power)
+                                lw_chamfer=lw_chamfer, kernel_size=kernel_size, power=power, sil_mode=sil_mode,
+                                sil_sigma=sil_sigma, sil_sigma_decay=sil_sigma_decay, sil_sigma_min=sil_sigma_min)
         with torch.no_grad():
             cand_iou.append(fit()[1].detach())
             cand_verts.append(fit.apply_transformation().detach())

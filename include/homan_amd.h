@@ -304,6 +304,26 @@ int hm_softsil_fwd(const float* verts, const int* faces, const float* K, int B, 
 int hm_softsil_bwd(const float* verts, const int* faces, const float* K, int B, int V, int F, int S, float orig_size,
                    float znear, float zfar, const float* sigma, const float* alpha, const float* grad_alpha,
                    const int* adj_off, const int* adj_items, float* grad_verts, void* workspace, hipStream_t stream);
+/* Soft mode of the object-pose initialisation (csrc/softpose.hip; homan_amd/pose_optimization.py, sil_mode="soft").
+ * hm_softsil_pose_terms: one pass over the soft images alpha (N,S,S) of hm_softsil_fwd - the candidates of one fit, rendered at
+ *   the mask's own size S, orig_size 1 - with ONE shared keep / ref image (S,S) each (0 / 1: keep = mask >= 0, ref = mask > 0),
+ *   image = keep * alpha:  terms (N,2) = {mask, IoU}, mask = sum (image - ref)^2, IoU = sum image ref / (sum clamp(image + ref,
+ *   0, 1) + 1e-6) - hm_sil_reduce's frame_out layout, so hm_pose_keep_best(_log) takes it with stride 2;
+ *   grad (N,S,S) = d mask_i / d alpha_i = 2 keep (keep alpha_i - ref), every sample written: the grad_alpha of hm_softsil_bwd.
+ *   alpha is read once and grad written once, with 16-byte accesses where S * S is a multiple of 4 and the four images are
+ *   16-byte aligned; the samples are dealt to lanes in the same way otherwise.  Per-workgroup partial sums are added by the
+ *   candidate's last workgroup in ascending workgroup index, no floating-point atomics: a candidate's row of terms and its grad
+ *   are the same bits whatever N is and from call to call.
+ *   1 <= S <= 4096, 1 <= N <= 65535, no NULL pointer, else HM_ERR_BAD_ARG: nothing is launched, the outputs stay untouched.
+ *   workspace: hm_softsil_pose_workspace_bytes(N, S) bytes (0 for shapes outside that range), zero-filled once (self-resetting
+ *   tickets).
+ * hm_sigma_anneal: sigma[0] <- max(sigma[0] * decay, sigma_min) in float32, one multiply and one max, on the stream: the blur
+ *   schedule of a captured loop (sigma is the device float the soft kernels read when they run).  0 < decay <= 1,
+ *   0 <= sigma_min < inf, else HM_ERR_BAD_ARG.  A sigma that underflows to 0 renders empty, see above. */
+size_t hm_softsil_pose_workspace_bytes(int N, int S);
+int hm_softsil_pose_terms(const float* alpha, const float* keep, const float* ref, int N, int S, float* terms, float* grad,
+                          void* workspace, hipStream_t stream);
+int hm_sigma_anneal(float* sigma, float decay, float sigma_min, hipStream_t stream);
 
 /* ------------------------------------------------------------------ small losses (value + unit gradient in one launch)
  * workspace for all of them: hm_reduce_workspace_bytes(), zero-filled once. */
