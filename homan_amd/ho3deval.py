@@ -7,7 +7,9 @@ The reference script runs at import and needs the datasets; its behaviour is res
   - every frame is scored (evalho3drecons.py:120-190): object vertex distance and ADD-S through `ops.cloud_metrics`
     (prediction first, ground truth second, :131-133), hand-root error (:160), penetration depth and contact of the hand in
     the object's SDF (:176-188) - in chunks of frames, one SDF scene per chunk size instead of two grids per frame;
-  - `dump` (ho3devalutils.py:16-33) writes the `pred.json` / zip of the HO-3D server.
+  - `dump` (ho3devalutils.py:16-33) writes the `pred.json` / zip of the HO-3D server;
+  - beyond the reference: with the ground-truth hand, `evaluate_sequence_protocol` adds what that server scores (aligned
+    joint and mesh errors, F-scores; homan_amd/handmetrics.py) and `protocol_summary` forms its table.
 Predictions are moved to the HO-3D frame by right-multiplying with camextr = diag(1, -1, -1) (:101), a sign flip of y and z;
 the 21 joints go from this project's order to HO-3D's with `UNORDER_IDXS` (:105-107, row 12 is named twice).
 Divergences: a sequence with ONE key frame holds that key over all frames (the reference raises a NameError); a zero
@@ -24,7 +26,7 @@ from collections import defaultdict
 import numpy as np
 import torch
 
-from . import constants, lib, ops
+from . import constants, handmetrics, lib, ops
 
 CAMEXTR_SIGNS = (1.0, -1.0, -1.0)                # diagonal of evalho3drecons.py:101
 UNORDER_IDXS = (0, 5, 6, 7, 10, 11, 12, 17, 18, 19, 13, 14, 15, 1, 2, 3, 4, 8, 12, 16, 20)       # ours -> HO-3D (:105-107)
@@ -108,16 +110,18 @@ def _faces(faces):
     return faces.reshape(1, -1, 3)
 
 
-def evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk=512):
-    """Scores of every frame of one sequence (evalho3drecons.py:120-190) and its export arrays.
+def _hand_gt(gt, name, pred):
+    """ground-truth joints / vertices of every frame -> fp32 on the prediction's device, shaped like it (None stays None)"""
+    if gt is None:
+        return None
+    gt = torch.as_tensor(np.asarray(gt.cpu() if isinstance(gt, torch.Tensor) else gt))
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"{name}: expected {tuple(pred.shape)}, got {tuple(gt.shape)}")
+    return gt.to(device=pred.device, dtype=torch.float32).contiguous()
 
-    seq_res: {key frame: {"hand_verts3d" (778,3), "hand_joints3d" (21,3), "obj_verts3d" (Vo,3)}} fp32, camera frame;
-    gt_obj_verts (frame_nb, Vg, 3) and gt_hand_roots (frame_nb, 1, 3) or (frame_nb, 3): ground truth in the HO-3D frame,
-    i.e. after the script's `.dot(camextr)` (:122, :150); obj_faces (Fo,3), mano_faces_closed (Fh,3): topology of the
-    predicted object mesh and of the closed hand.  Frames are scored `chunk` at a time; a frame's values do not depend on
-    the chunk size.  Returns per-frame float64 arrays "obj_dist", "obj_add-s", "hand_root", "pen_depths", "has_contact"
-    (0 / 1) and fp32 "export_joints" (frame_nb, 21, 3) in HO-3D order, "export_verts" (frame_nb, 778, 3), both flipped:
-    the lists `dump` takes."""
+
+def _evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk, hand_gt=None):
+    """evaluate_sequence; hand_gt = (gt_hand_joints or None, gt_hand_verts or None, anchors) adds the protocol's per-frame arrays"""
     if chunk < 1:
         raise ValueError(f"chunk must be positive, got {chunk}")
     obj = interpolate_sequence(seq_res, frame_nb, "obj_verts3d", CAMEXTR_SIGNS)
@@ -129,7 +133,10 @@ def evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces,
         raise ValueError(f"gt_obj_verts: expected ({frame_nb}, Vg, 3), got {tuple(gt_obj.shape)}")
     gt_obj = gt_obj.to(device=dev, dtype=torch.float32).contiguous()       # (`torch.Tensor(gt_objverts).float()`, :133)
     hand_faces, object_faces = _faces(mano_faces_closed)[0], _faces(obj_faces)[0]
-    scenes, tabs, deepest = {}, [], []
+    gt_joints, gt_verts, anchors = hand_gt if hand_gt is not None else (None, None, None)
+    gt_joints = _hand_gt(gt_joints, "gt_hand_joints", joints)
+    gt_verts = _hand_gt(gt_verts, "gt_hand_verts", verts)
+    scenes, tabs, deepest, protocol = {}, [], [], defaultdict(list)
     with torch.cuda.device(dev):
         for f0 in range(0, frame_nb, chunk):
             n = min(chunk, frame_nb - f0)
@@ -138,14 +145,78 @@ def evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces,
                 scenes[n] = ops.CollisionContext(hand_faces.numpy(), object_faces, n, verts.shape[1], obj.shape[1], dev)
             depth = ops.collision_dist_values(verts[f0:f0 + n], obj[f0:f0 + n], scenes[n], constants.SDF_SCALE_FACTOR)[(1, 0)]
             deepest.append(depth.amax(dim=1))
+            if gt_joints is not None:
+                errs, _ = handmetrics.frame_errors(gt_joints[f0:f0 + n], joints[f0:f0 + n], anchors)
+                for tag, err in errs.items():
+                    protocol[f"joint_err{tag}"].append(err)
+            if gt_verts is not None:
+                errs, aligned = handmetrics.frame_errors(gt_verts[f0:f0 + n], verts[f0:f0 + n], scale_trans=False)
+                for tag, err in errs.items():
+                    protocol[f"mesh_err{tag}"].append(err)
+                for prefix, pred in (("f", verts[f0:f0 + n]), ("f_al", aligned)):
+                    tab = handmetrics.frame_fscores(gt_verts[f0:f0 + n], pred, handmetrics.F_THRESHOLDS)
+                    for t, th in enumerate(handmetrics.F_THRESHOLDS):
+                        protocol[f"{prefix}@{round(th * 1000):d}"].append(tab[:, t])
         tab = torch.cat(tabs)
         same_size = obj.shape[1] == gt_obj.shape[1]
         scores = torch.stack([tab[:, 3] if same_size else tab[:, 2], tab[:, 2], torch.cat(deepest).double()]).cpu().numpy()
         export_joints, export_verts = joints.cpu().numpy(), verts.cpu().numpy()
+        protocol = {key: torch.cat(parts).cpu().numpy() for key, parts in protocol.items()}
     roots = np.asarray(gt_hand_roots.cpu() if isinstance(gt_hand_roots, torch.Tensor) else gt_hand_roots).reshape(frame_nb, -1, 3)
     hand_root = np.linalg.norm(export_joints[:, 0] - roots[:, 0], axis=-1).astype(np.float64)
-    return {"obj_dist": scores[0], "obj_add-s": scores[1], "hand_root": hand_root, "pen_depths": scores[2],
+    res = {"obj_dist": scores[0], "obj_add-s": scores[1], "hand_root": hand_root, "pen_depths": scores[2],
             "has_contact": (scores[2] > 0).astype(np.float64), "export_joints": export_joints, "export_verts": export_verts}
+    res.update(protocol)
+    return res
+
+
+def evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk=512):
+    """Scores of every frame of one sequence (evalho3drecons.py:120-190) and its export arrays.
+
+    seq_res: {key frame: {"hand_verts3d" (778,3), "hand_joints3d" (21,3), "obj_verts3d" (Vo,3)}} fp32, camera frame;
+    gt_obj_verts (frame_nb, Vg, 3) and gt_hand_roots (frame_nb, 1, 3) or (frame_nb, 3): ground truth in the HO-3D frame,
+    i.e. after the script's `.dot(camextr)` (:122, :150); obj_faces (Fo,3), mano_faces_closed (Fh,3): topology of the
+    predicted object mesh and of the closed hand.  Frames are scored `chunk` at a time; a frame's values do not depend on
+    the chunk size.  Returns per-frame float64 arrays "obj_dist", "obj_add-s", "hand_root", "pen_depths", "has_contact"
+    (0 / 1) and fp32 "export_joints" (frame_nb, 21, 3) in HO-3D order, "export_verts" (frame_nb, 778, 3), both flipped:
+    the lists `dump` takes."""
+    return _evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk)
+
+
+PROTOCOL_KEYS = ("joint_err", "joint_err_al", "joint_err_sc_tr", "mesh_err", "mesh_err_al", "f@5", "f@15", "f_al@5", "f_al@15")
+
+
+def evaluate_sequence_protocol(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk=512,
+                               gt_hand_joints=None, gt_hand_verts=None, anchors=(0, 4)):
+    """`evaluate_sequence` with the hand protocol's per-frame arrays (homan_amd/handmetrics.py) added, computed chunk by chunk
+    from the interpolated frames already on the device.  gt_hand_joints (frame_nb, 21, 3): HO-3D frame, HO-3D joint order (that
+    of "export_joints") -> "joint_err", "joint_err_al", "joint_err_sc_tr" (frame_nb, 21) float64 per-joint errors raw,
+    similarity-aligned and scale-and-translation-aligned on the joint rows `anchors`.  gt_hand_verts (frame_nb, 778, 3) ->
+    "mesh_err", "mesh_err_al" (frame_nb, 778) and the per-frame F-scores "f@5", "f@15", "f_al@5", "f_al@15" (frame_nb,).
+    Either may be None; with both None the result is `evaluate_sequence`'s: same keys, same bits.  A frame's values do not
+    depend on the chunk size.  `protocol_summary` turns the arrays into the protocol's table."""
+    return _evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk,
+                              (gt_hand_joints, gt_hand_verts, anchors))
+
+
+def protocol_summary(per_frame, auc_max=0.05, auc_steps=100):
+    """The protocol's table from the arrays of `evaluate_sequence_protocol` (a dict, or a list of them in sequence order):
+    "xyz_mean3d", "xyz_auc", "xyz_al_mean3d", "xyz_al_auc", "xyz_sc_tr_mean3d", "xyz_sc_tr_auc", "mesh_mean3d", "mesh_auc",
+    "mesh_al_mean3d", "mesh_al_auc" (means over all frames and points; AUC of the PCK curve over [0, auc_max], counted exactly
+    on the device) and "f@5", "f@15", "f_al@5", "f_al@15" (means over the frames); only what the arrays hold."""
+    if isinstance(per_frame, dict):
+        per_frame = [per_frame]
+    table = {}
+    for key, name in (("joint_err", "xyz"), ("joint_err_al", "xyz_al"), ("joint_err_sc_tr", "xyz_sc_tr"), ("mesh_err", "mesh"),
+                      ("mesh_err_al", "mesh_al")):
+        if all(key in seq for seq in per_frame):
+            err = np.concatenate([np.asarray(seq[key], np.float64).reshape(-1) for seq in per_frame])
+            table[f"{name}_mean3d"] = float(err.mean())
+            table[f"{name}_auc"] = handmetrics.auc(err, auc_max, auc_steps)
+    for key in ("f@5", "f@15", "f_al@5", "f_al@15"):
+        if all(key in seq for seq in per_frame):
+            table[key] = float(np.concatenate([np.asarray(seq[key], np.float64).reshape(-1) for seq in per_frame]).mean())
+    return table
 
 
 def summarise(per_frame, unseen_from=None):

@@ -990,3 +990,78 @@ def keyframe_interp(key_vals, key_frames, frame_nb, gather=None, signs=(1.0, 1.0
                          f"strictly and end at or before frame_nb = {frame_nb}; gather must index [0, {N}); signs must be +-1")
     _lib.check(rc, "hm_keyframe_interp")
     return out
+
+
+ALIGN_MODES = {"similarity": 0, "rigid_similarity": 1, "scale_trans": 2}
+
+
+def _check_pair(pred, gt):
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError(f"{name}: expected a float tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name}: expected a non-empty (B, N, 3) tensor, got {tuple(t.shape)}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred and gt differ in shape: {tuple(pred.shape)} vs {tuple(gt.shape)}")
+
+
+def procrustes_align(pred, gt, mode=0, anchors=(0, 4)):
+    """Per-frame alignment of pred (B,N,3) onto gt (B,N,3) (no grad; csrc/evalalign.hip, formulas in include/homan_amd.h) ->
+    aligned (B,N,3) fp32, err (B,N) float64 = |aligned_i - gt_i| before `aligned` is rounded, xform (B,13) float64
+    {s, R row-major, t} with aligned = s * pred @ R.T + t.  mode 0 / "similarity": orthogonal factor, reflections allowed;
+    1 / "rigid_similarity": proper rotation; 2 / "scale_trans": scale and translation off the two `anchors` (rows of N)."""
+    mode = ALIGN_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"mode must be one of {sorted(ALIGN_MODES)} or 0 / 1 / 2, got {mode!r}")
+    _check_pair(pred, gt)
+    B, N = pred.shape[0], pred.shape[1]
+    a, b = (int(v) for v in anchors)
+    if mode == 2 and not (0 <= a < N and 0 <= b < N):
+        raise ValueError(f"anchors {(a, b)} out of range for {N} points")
+    pred, gt = _f32(pred.detach()), _f32(gt.detach())
+    dev = pred.device
+    aligned = torch.empty(B, N, 3, device=dev)
+    err = torch.empty(B, N, dtype=torch.float64, device=dev)
+    xform = torch.empty(B, 13, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().hm_procrustes_align(_lib.ptr(pred), _lib.ptr(gt), B, N, mode, a, b, _lib.ptr(aligned), _lib.ptr(err),
+                                              _lib.ptr(xform), _lib.stream()), "hm_procrustes_align")
+    return aligned, err, xform
+
+
+def threshold_counts(dist, val_max, steps=100):
+    """Exact counts[k] = #(dist_i <= t_k) over t = np.linspace(0, val_max, steps) (no grad; csrc/evalalign.hip) -> (steps,)
+    int64 on the device of `dist` (any shape, fp32 or float64; NaN counts nowhere)."""
+    if not isinstance(dist, torch.Tensor) or dist.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"dist: expected a float32 or float64 tensor, got {getattr(dist, 'dtype', type(dist))}")
+    steps = int(steps)
+    if not 2 <= steps <= 1024:
+        raise ValueError(f"steps must lie in [2, 1024], got {steps}")
+    vmax = np.array([val_max], dtype=np.float64)
+    if not (np.isfinite(vmax[0]) and vmax[0] > 0):
+        raise ValueError(f"val_max must be positive and finite, got {val_max}")
+    dist = dist.detach().contiguous()
+    counts = torch.empty(steps, dtype=torch.int64, device=dist.device)
+    _lib.check(_lib.lib().hm_threshold_counts(_lib.ptr(dist) if dist.numel() else None, dist.numel(),
+                                              int(dist.dtype == torch.float64), vmax.ctypes.data, steps, _lib.ptr(counts),
+                                              _lib.stream()), "hm_threshold_counts")
+    return counts
+
+
+def fscore(x_d2, y_d2, thresholds):
+    """x_d2 (B,N), y_d2 (B,M): the squared fp32 nearest-neighbour distances of `cloud_metrics(pred, gt, per_point=True)`;
+    thresholds: 1 to 8 floats -> (B,T,3) float64 {precision, recall, F}, strict < (no grad; csrc/evalalign.hip)."""
+    ths = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+    if not 1 <= ths.shape[0] <= 8:
+        raise ValueError(f"between 1 and 8 thresholds, got {ths.shape[0]}")
+    for name, t in (("x_d2", x_d2), ("y_d2", y_d2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name}: expected a non-empty (B, N) float32 tensor, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if x_d2.shape[0] != y_d2.shape[0]:
+        raise ValueError(f"batch sizes differ: {x_d2.shape[0]} vs {y_d2.shape[0]}")
+    x_d2, y_d2 = x_d2.detach().contiguous(), y_d2.detach().contiguous()
+    B, T = x_d2.shape[0], ths.shape[0]
+    out = torch.empty(B, T, 3, dtype=torch.float64, device=x_d2.device)
+    _lib.check(_lib.lib().hm_fscore(_lib.ptr(x_d2), _lib.ptr(y_d2), B, x_d2.shape[1], y_d2.shape[1], ths.ctypes.data, T,
+                                    _lib.ptr(out), _lib.stream()), "hm_fscore")
+    return out

@@ -388,6 +388,40 @@ int hm_align_stats(const float* gt_hand, const float* pred_hand, int B, int hand
 int hm_keyframe_interp(const float* key_vals, const int* key_frames, int K, int N, int frame_nb, const int* gather, int M,
                        const float* signs, int out_f64, int* key_frames_dev, int* gather_dev, void* out, hipStream_t stream);
 
+/* ------------------------------------------------------------------ hand protocol metrics (csrc/evalalign.hip)
+ * The FreiHAND / HO-3D evaluation arithmetic.  The protocol's script is not in the reference tree: the formulas below ARE the
+ * definition, pinned by the float64 NumPy restatement of tests/handmetrics_ref.py.  Every floating-point
+ * sum is a double formed in a fixed order by the frame's own workgroup: two calls return the same bits, and a frame's values
+ * do not depend on the other frames of the call.
+ *
+ * hm_procrustes_align: pred, gt (B,N,3) fp32 -> aligned (B,N,3) fp32, err (B,N) double = |aligned_i - gt_i| taken on the
+ * double value of the aligned point before it is rounded for `aligned`, xform (B,13) double {s, R row-major, t} with
+ * aligned = s * pred * R^T + t (row vectors).  Each output is optional (NULL).
+ *   mode 0, similarity with an orthogonal factor (reflections allowed; scipy's orthogonal_procrustes on normalised sets):
+ *     mu_g, mu_p the means, a = (gt - mu_g) / s1, b = (pred - mu_p) / s2 with s1 = |gt - mu_g|_F + 1e-8, s2 = |pred - mu_p|_F
+ *     + 1e-8, M = b^T a = U S V^T, Q = U V^T, sigma = trace S, aligned = (b Q) * sigma * s1 + mu_g;
+ *   mode 1, the same with a proper rotation: det(U V^T) < 0 flips the last column of U and the smallest singular value;
+ *   mode 2, scale and translation off two anchor points: k = |gt[b] - gt[a]| / |pred[b] - pred[a]| (1 when the denominator is
+ *     0), aligned = k * (pred - pred[a]) + gt[a]; R = I.  anchor_a, anchor_b must lie in [0, N) (read in mode 2 only).
+ * The SVD is a one-sided Jacobi iteration in double: sweeps over the column pairs (0,1), (0,2), (1,2) until one sweep finds
+ * every pair orthogonal to (p.q)^2 <= 2^-100 |p|^2 |q|^2, 30 sweeps at most.  A rank-deficient M (N = 1, collinear or coplanar
+ * sets, zero) has its left vectors completed to an orthogonal U: the outputs are finite and a minimiser; N = 1 gives gt.
+ * B < 1, N < 1, a NULL input, a mode outside 0..2 or an anchor out of range: HM_ERR_BAD_ARG, nothing launched. */
+int hm_procrustes_align(const float* pred, const float* gt, int B, int N, int mode, int anchor_a, int anchor_b, float* aligned,
+                        double* err, double* xform, hipStream_t stream);
+/* counts[k] = number of dist_i <= t_k, t = np.linspace(0, val_max, steps): t_k = k * (val_max / (steps - 1)) in double and
+ * t_{steps-1} = val_max.  dist: n values on the device, fp32 (is_f64 == 0) or double; val_max: HOST pointer to one double
+ * (> 0, finite), read during the call; counts: `steps` unsigned 64-bit integers on the device.  Exact: the bin guessed by a
+ * division is corrected by comparing against t_k itself.  NaN counts nowhere.  2 <= steps <= 1024; n == 0 is HM_OK, all
+ * zero.  PCK = counts / n and AUC = trapz(PCK, t) / val_max are the host's to form from the integers. */
+int hm_threshold_counts(const void* dist, long n, int is_f64, const double* val_max, int steps, void* counts, hipStream_t stream);
+/* F-scores off the squared fp32 nearest-neighbour distances hm_cloud_metrics writes: x_d2 (B,N) of the prediction, y_d2 (B,M)
+ * of the ground truth; thresholds: HOST float[T], 1 <= T <= 8, read during the call.  out (B,T,3) double = {precision, recall,
+ * F}: precision = #(sqrt((double)x_d2) < (double)th) / N, recall the same over y_d2 / M, F = 2 p r / (p + r), 0 when
+ * p + r = 0.  Strict <. */
+int hm_fscore(const float* x_d2, const float* y_d2, int B, int N, int M, const float* thresholds, int T, double* out,
+              hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
