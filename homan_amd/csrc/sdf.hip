@@ -17,6 +17,7 @@
 //     wave: 127 us; the three passes take ~40.)
 // Conventions identical to oracle/csrc/sdf.c (voxel centres -1+(i+0.5)*2/N, phi[z][y][x], half-open orientation rule).
 #include "hm_common.h"
+#include "inside_test.h"      // orient2, ray_x_crosses
 
 #define SDF_N 32
 #define SDF_THREADS 256
@@ -56,36 +57,6 @@ __device__ __forceinline__ float point_triangle_distance(const float* x0, const 
     if (w23 > 0.0f) return fminf(seg_dist(x0, x1, x2), seg_dist(x0, x1, x3));
     if (w31 > 0.0f) return fminf(seg_dist(x0, x1, x2), seg_dist(x0, x2, x3));
     return fminf(seg_dist(x0, x1, x3), seg_dist(x0, x2, x3));
-}
-
-__device__ __forceinline__ int orient2(float x1, float y1, float x2, float y2, float* tsa)
-{
-    *tsa = y1 * x2 - x1 * y2;
-    if (*tsa > 0.0f) return 1;
-    if (*tsa < 0.0f) return -1;
-    if (y2 > y1) return 1;
-    if (y2 < y1) return -1;
-    if (x1 > x2) return 1;
-    if (x1 < x2) return -1;
-    return 0;
-}
-
-__device__ __forceinline__ bool ray_x_crosses(float cy, float cz, const float* v1, const float* v2, const float* v3,
-                                              float* xhit)
-{
-    const float y1 = v1[1] - cy, z1 = v1[2] - cz, y2 = v2[1] - cy, z2 = v2[2] - cz, y3 = v3[1] - cy, z3 = v3[2] - cz;
-    float a, b, g;
-    const int sa = orient2(y2, z2, y3, z3, &a);
-    if (sa == 0) return false;
-    const int sb = orient2(y3, z3, y1, z1, &b);
-    if (sb != sa) return false;
-    const int sc = orient2(y1, z1, y2, z2, &g);
-    if (sc != sa) return false;
-    const float sum = a + b + g;
-    if (sum == 0.0f) return false;
-    const float fa = a / sum, fb = b / sum, fc = g / sum;
-    *xhit = fa * v1[0] + fb * v2[0] + fc * v3[0];
-    return true;
 }
 
 __device__ __forceinline__ float voxel_centre(int i) { return -1.0f + ((float)i + 0.5f) * (2.0f / (float)SDF_N); }

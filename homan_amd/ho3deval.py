@@ -9,7 +9,8 @@ The reference script runs at import and needs the datasets; its behaviour is res
     the object's SDF (:176-188) - in chunks of frames, one SDF scene per chunk size instead of two grids per frame;
   - `dump` (ho3devalutils.py:16-33) writes the `pred.json` / zip of the HO-3D server;
   - beyond the reference: with the ground-truth hand, `evaluate_sequence_protocol` adds what that server scores (aligned
-    joint and mesh errors, F-scores; homan_amd/handmetrics.py) and `protocol_summary` forms its table.
+    joint and mesh errors, F-scores; homan_amd/handmetrics.py) and `protocol_summary` forms its table;
+    `evaluate_sequence_plausibility` scores what needs no ground truth: intersection volume, penetration depth, contact.
 Predictions are moved to the HO-3D frame by right-multiplying with camextr = diag(1, -1, -1) (:101), a sign flip of y and z;
 the 21 joints go from this project's order to HO-3D's with `UNORDER_IDXS` (:105-107, row 12 is named twice).
 Divergences: a sequence with ONE key frame holds that key over all frames (the reference raises a NameError); a zero
@@ -26,7 +27,7 @@ from collections import defaultdict
 import numpy as np
 import torch
 
-from . import constants, handmetrics, lib, ops
+from . import constants, handmetrics, lib, ops, pointmetrics
 
 CAMEXTR_SIGNS = (1.0, -1.0, -1.0)                # diagonal of evalho3drecons.py:101
 UNORDER_IDXS = (0, 5, 6, 7, 10, 11, 12, 17, 18, 19, 13, 14, 15, 1, 2, 3, 4, 8, 12, 16, 20)       # ours -> HO-3D (:105-107)
@@ -181,6 +182,32 @@ def evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces,
     (0 / 1) and fp32 "export_joints" (frame_nb, 21, 3) in HO-3D order, "export_verts" (frame_nb, 778, 3), both flipped:
     the lists `dump` takes."""
     return _evaluate_sequence(seq_res, frame_nb, gt_obj_verts, gt_hand_roots, obj_faces, mano_faces_closed, chunk)
+
+
+def evaluate_sequence_plausibility(seq_res, frame_nb, obj_faces, mano_faces_closed, chunk=512, voxel=0.005):
+    """Physical-plausibility scores of every interpolated frame of one sequence; no ground truth is needed.  seq_res, obj_faces,
+    mano_faces_closed and chunk as `evaluate_sequence` (the frames are interpolated and flipped the same way) ->
+    "inter_volume" (frame_nb,) float64, m^3: hand-object intersection volume on the world-anchored lattice of pitch `voxel`
+    (`pointmetrics.get_volume_metrics`); "pen_depth" and "has_contact" (0 / 1), float64: what `pointmetrics.get_inter_metrics`
+    gives, the "pen_depths" / "has_contact" of `evaluate_sequence`; and their means over the frames, "inter_volume_mean",
+    "pen_depth_mean", "has_contact_mean".  A frame's values do not depend on the chunk size."""
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    ops.voxel_pitch(voxel)
+    obj = interpolate_sequence(seq_res, frame_nb, "obj_verts3d", CAMEXTR_SIGNS)
+    verts = interpolate_sequence(seq_res, frame_nb, "hand_verts3d", CAMEXTR_SIGNS)
+    hand_faces, object_faces = _faces(mano_faces_closed), _faces(obj_faces)
+    volumes, depths, contacts = [], [], []
+    for f0 in range(0, frame_nb, chunk):
+        hand, thing = verts[f0:f0 + chunk], obj[f0:f0 + chunk]
+        volumes += pointmetrics.get_volume_metrics(hand, thing, hand_faces, object_faces, voxel=voxel)["inter_volumes"]
+        inter = pointmetrics.get_inter_metrics(hand, thing, hand_faces, object_faces)
+        depths += inter["pen_depths"]
+        contacts += inter["has_contact"]
+    res = {"inter_volume": np.asarray(volumes, np.float64), "pen_depth": np.asarray(depths, np.float64),
+           "has_contact": np.asarray(contacts, np.float64)}
+    res.update({f"{key}_mean": float(vals.mean()) for key, vals in list(res.items())})
+    return res
 
 
 PROTOCOL_KEYS = ("joint_err", "joint_err_al", "joint_err_sc_tr", "mesh_err", "mesh_err_al", "f@5", "f@15", "f_al@5", "f_al@15")

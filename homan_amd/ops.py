@@ -1065,3 +1065,101 @@ def fscore(x_d2, y_d2, thresholds):
     _lib.check(_lib.lib().hm_fscore(_lib.ptr(x_d2), _lib.ptr(y_d2), B, x_d2.shape[1], y_d2.shape[1], ths.ctypes.data, T,
                                     _lib.ptr(out), _lib.stream()), "hm_fscore")
     return out
+
+
+VOXEL_MAX_INDEX = 1 << 22        # beyond it ((float)i + 0.5f) * pitch is no longer a clean fp32 lattice (csrc/solidvox.hip)
+
+
+def _check_mesh(verts, faces):
+    """verts: non-empty float (B,V,3) tensor; faces: (F,3) integers in [0, V), host array or tensor -> int32 numpy (F,3)"""
+    if not isinstance(verts, torch.Tensor) or not verts.is_floating_point():
+        raise ValueError(f"verts: expected a float tensor, got {getattr(verts, 'dtype', type(verts))}")
+    if verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[0] < 1 or verts.shape[1] < 1:
+        raise ValueError(f"verts: expected a non-empty (B, V, 3) tensor, got {tuple(verts.shape)}")
+    faces = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.dtype.kind not in "iu":
+        raise ValueError(f"faces: expected a non-empty integer (F, 3) array, got {faces.dtype} {faces.shape}")
+    if faces.min() < 0 or faces.max() >= verts.shape[1]:
+        raise ValueError(f"faces index [{faces.min()}, {faces.max()}], outside the {verts.shape[1]} vertices")
+    return np.ascontiguousarray(faces, dtype=np.int32)
+
+
+def voxel_pitch(pitch):
+    """the pitch rounded to fp32 once: that value is h everywhere (ValueError unless it is finite and positive)"""
+    with np.errstate(over="ignore"):
+        h = np.float32(pitch)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError(f"pitch must be positive and finite in fp32, got {pitch}")
+    return h
+
+
+def mesh_volume(verts, faces):
+    """Exact volume of B closed meshes of one topology (no grad; csrc/solidvox.hip): verts (B,V,3), faces (F,3) -> (B,) float64
+    |sum_f det(p1 - r, p2 - r, p3 - r)| / 6 about each frame's vertex 0, in double, summed in one fixed order."""
+    faces = _check_mesh(verts, faces)
+    verts = _f32(verts.detach())
+    B, V = verts.shape[0], verts.shape[1]
+    out = torch.empty(B, dtype=torch.float64, device=verts.device)
+    fdev = torch.from_numpy(faces).to(verts.device)
+    _lib.check(_lib.lib().hm_mesh_volume(_lib.ptr(verts), _lib.ptr(fdev), B, V, faces.shape[0], _lib.ptr(out), _lib.stream()),
+               "hm_mesh_volume")
+    return out
+
+
+def solid_voxels(verts, faces, pitch, boxes, dims=None, out=None):
+    """Solid voxelisation of B closed meshes on the world-anchored lattice of `pitch` (no grad; csrc/solidvox.hip, the rules in
+    include/homan_amd.h): verts (B,V,3), faces (F,3), boxes (B,6) host integers {i0, j0, k0, nx, ny, nz} per frame, dims =
+    (NWX, NY, NZ) launch-wide (default: the smallest that hold every box) -> words (B, NZ, NY, NWX) int32 holding the 32-bit
+    patterns: bit t of word w in row (k, j) is voxel (i0 + 32w + t, j0 + j, k0 + k), centre ((float)i + 0.5f) * pitch.  out:
+    a contiguous int32 device tensor of that shape to fill instead of a new one."""
+    faces = _check_mesh(verts, faces)
+    h = voxel_pitch(pitch)
+    B, V = verts.shape[0], verts.shape[1]
+    boxes = np.asarray(boxes)
+    if boxes.shape != (B, 6) or boxes.dtype.kind not in "iu":
+        raise ValueError(f"boxes: expected integers of shape ({B}, 6), got {boxes.dtype} {boxes.shape}")
+    boxes = boxes.astype(np.int64)
+    if (boxes[:, 3:] < 0).any():
+        raise ValueError("boxes: negative extent")
+    if (boxes[:, :3] < -VOXEL_MAX_INDEX).any() or (boxes[:, :3] + boxes[:, 3:] > VOXEL_MAX_INDEX).any():
+        raise ValueError(f"boxes: voxel index beyond +-{VOXEL_MAX_INDEX}")
+    need = (int(-(-boxes[:, 3].max() // 32)), int(boxes[:, 4].max()), int(boxes[:, 5].max()))
+    nwx, ny, nz = need if dims is None else (int(d) for d in dims)
+    if nwx < need[0] or ny < need[1] or nz < need[2]:
+        raise ValueError(f"dims {(nwx, ny, nz)} do not hold the boxes, which need {need}")
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32)
+    verts = _f32(verts.detach())
+    dev = verts.device
+    if out is not None and (out.dtype != torch.int32 or tuple(out.shape) != (B, nz, ny, nwx) or not out.is_contiguous()
+                            or out.device != dev):
+        raise ValueError(f"out: expected a contiguous int32 tensor of shape {(B, nz, ny, nwx)} on {dev}")
+    words = torch.empty(B, nz, ny, nwx, dtype=torch.int32, device=dev) if out is None else out
+    boxes_dev = torch.empty(B, 6, dtype=torch.int32, device=dev)
+    fdev = torch.from_numpy(faces).to(dev)
+    _lib.check(_lib.lib().hm_solid_voxels(_lib.ptr(verts), _lib.ptr(fdev), B, V, faces.shape[0], float(h), boxes.ctypes.data,
+                                          nwx, ny, nz, _lib.ptr(boxes_dev), _lib.ptr(words) if words.numel() else None,
+                                          _lib.stream()), "hm_solid_voxels")
+    return words
+
+
+def voxel_overlap(a, b):
+    """Words of two voxelisations of one region -> (B,3) int64 {popcount(a & b), popcount(a), popcount(b)} per frame (no grad;
+    csrc/solidvox.hip).  b (B, ...) int32; a of the same shape, or (S, B, ...): S voxelisations that are OR-ed first."""
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError(f"{name}: expected an int32 tensor of words, got {getattr(t, 'dtype', type(t))}")
+    if b.dim() < 1 or b.shape[0] < 1:
+        raise ValueError(f"b: expected (B, ...) with B >= 1, got {tuple(b.shape)}")
+    if a.shape == b.shape:
+        sets = 1
+    elif a.dim() == b.dim() + 1 and a.shape[1:] == b.shape and a.shape[0] >= 1:
+        sets = a.shape[0]
+    else:
+        raise ValueError(f"a {tuple(a.shape)} is neither b's shape {tuple(b.shape)} nor (S,) + it")
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    B = b.shape[0]
+    counts = torch.empty(B, 3, dtype=torch.int64, device=b.device)
+    per_frame = b.numel() // B
+    _lib.check(_lib.lib().hm_voxel_overlap(_lib.ptr(a) if per_frame else None, sets, _lib.ptr(b) if per_frame else None, B,
+                                           per_frame, _lib.ptr(counts), _lib.stream()), "hm_voxel_overlap")
+    return counts

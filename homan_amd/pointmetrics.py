@@ -7,6 +7,7 @@ search in both directions (`hm_cloud_metrics`, csrc/pointmetrics.hip) and the al
 the object's signed-distance grid.  Inputs are torch tensors on any device and of any float dtype; they are moved to the GPU
 as contiguous fp32, and each call syncs with the host once.  There is no CPU path: without a GPU these functions raise.
 """
+import numpy as np
 import torch
 
 from . import constants, lib, ops
@@ -109,3 +110,90 @@ def get_align_metrics(gt_hand_verts, pred_hand_verts, gt_obj_verts, pred_obj_ver
         tab = ops.cloud_metrics(pred_o, gt_o, aff_x=aff_pred, aff_y=aff_gt)
         values = torch.cat([hand_mean, tab[:, 0] + tab[:, 1]]).cpu().tolist()
     return {"hand_mean_aligned": values[:hand_nb * frames], "obj_chamfer_aligned": values[hand_nb * frames:]}
+
+
+def index_boxes(lo, hi, h):
+    """fp32 bounds (..., 3) of meshes -> inclusive voxel index boxes (first, last), int64: floor(min / h) - 1 .. floor(max / h)
+    + 1 per axis, the division in double.  The one-voxel margin absorbs the rounding of the division and of the fp32 centres."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("vertices are not finite")
+    first, last = np.floor(lo / float(h)) - 1, np.floor(hi / float(h)) + 1
+    if max(np.abs(first).max(), np.abs(last).max()) > ops.VOXEL_MAX_INDEX:
+        raise ValueError(f"voxel index beyond +-{ops.VOXEL_MAX_INDEX}: the mesh is too far from the origin for a pitch of {h}")
+    return first.astype(np.int64), last.astype(np.int64)
+
+
+def common_boxes(verts_hands, verts_object, h):
+    """device (B, N, 3) vertices of all hands of each frame and (B, Vo, 3) of the object -> (boxes (B,6) int64 {i0, j0, k0, nx,
+    ny, nz}, (NWX, NY, NZ)): per frame the intersection of the two meshes' index boxes, extents 0 where they do not meet, and
+    the launch dimensions that hold every frame.  One read-back."""
+    bounds = torch.stack([verts_hands.amin(1), verts_hands.amax(1), verts_object.amin(1), verts_object.amax(1)], 1).cpu().numpy()
+    hand_first, hand_last = index_boxes(bounds[:, 0], bounds[:, 1], h)
+    obj_first, obj_last = index_boxes(bounds[:, 2], bounds[:, 3], h)
+    first = np.maximum(hand_first, obj_first)
+    extent = np.minimum(hand_last, obj_last) - first + 1
+    extent[(extent <= 0).any(1)] = 0                                        # the boxes do not meet: nothing to voxelise
+    return (np.concatenate([first, extent], 1),
+            (int(-(-extent[:, 0].max() // 32)), int(extent[:, 1].max()), int(extent[:, 2].max())))
+
+
+def get_volume_metrics(verts_person, verts_object, faces_person, faces_object, voxel=0.005, max_bytes=256 << 20):
+    """Intersection volume of hand(s) and object from solid voxelisations on one world-anchored lattice of pitch `voxel`
+    (ObMan's physical-plausibility score), with the exact mesh volumes beside it.  Inputs as `get_inter_metrics`:
+    verts_person (B*hand_nb, Vh, 3) frame-major, verts_object (B, Vo, 3), faces_person (hand_nb, Fh, 3) closed hand faces,
+    faces_object (>=1, Fo, 3)  ->  {"inter_volumes", "hand_volumes", "obj_volumes"}: lists of B floats, m^3.
+
+    inter_volume = popcount(hand & object) * h^3 (h = fp32(voxel), the cube in double) over the intersection of the two
+    meshes' index boxes; each hand is voxelised separately and the hands are OR-ed.  Frames whose boxes do not meet score 0
+    and are not voxelised.  hand_volumes: exact mesh volumes summed over the hands; obj_volumes: the object's.  The definitions
+    are in include/homan_amd.h (csrc/solidvox.hip).  Frames are walked in chunks whose word arrays fit `max_bytes`; a
+    frame's values do not depend on the chunking.  One read-back for the boxes, one for the results."""
+    verts_person, verts_object = torch.as_tensor(verts_person), torch.as_tensor(verts_object)
+    _check_clouds(verts_person=verts_person, verts_object=verts_object)
+    h = ops.voxel_pitch(voxel)
+    scenes = verts_object.shape[0]
+    hands = verts_person.shape[0] // scenes
+    if hands < 1 or hands > 3 or hands * scenes != verts_person.shape[0]:
+        raise ValueError(f"{verts_person.shape[0]} hands for {scenes} frames")
+    if int(max_bytes) < 1:
+        raise ValueError(f"max_bytes must be positive, got {max_bytes}")
+    faces_person = np.asarray(torch.as_tensor(faces_person).cpu())
+    if faces_person.ndim == 2:
+        faces_person = faces_person[None]
+    hand_faces = [faces_person[k % faces_person.shape[0]] for k in range(hands)]
+    obj_faces = np.asarray(torch.as_tensor(faces_object).cpu())
+    obj_faces = obj_faces[0] if obj_faces.ndim == 3 else obj_faces
+    person, obj = _on_gpu(verts_person, verts_object)
+    with torch.cuda.device(obj.device):
+        # hand k of every frame as its own contiguous batch (the voxeliser and the volume take one topology per call)
+        per_hand = [person.reshape(scenes, hands, -1, 3)[:, k].contiguous() for k in range(hands)]
+        boxes, dims = common_boxes(person.reshape(scenes, -1, 3), obj, h)
+        extent = boxes[:, 3:]
+        frame_bytes = 4 * dims[0] * dims[1] * dims[2] * (hands + 1)
+        if frame_bytes > int(max_bytes):
+            raise ValueError(f"one frame needs {frame_bytes} bytes of voxel words at a pitch of {h}; max_bytes is {max_bytes}")
+        volumes = [ops.mesh_volume(v, f) for v, f in zip(per_hand, hand_faces)] + [ops.mesh_volume(obj, obj_faces)]
+        counts = []
+        if frame_bytes:
+            chunk = max(int(max_bytes) // frame_bytes, 1)
+            for f0 in range(0, scenes, chunk):
+                sl = slice(f0, min(f0 + chunk, scenes))
+                if not extent[sl].any():
+                    counts.append(torch.zeros(sl.stop - sl.start, 3, dtype=torch.int64, device=obj.device))
+                    continue
+                hand_words = torch.empty(hands, sl.stop - sl.start, dims[2], dims[1], dims[0], dtype=torch.int32,
+                                         device=obj.device)
+                for k in range(hands):
+                    ops.solid_voxels(per_hand[k][sl], hand_faces[k], h, boxes[sl], dims, out=hand_words[k])
+                counts.append(ops.voxel_overlap(hand_words, ops.solid_voxels(obj[sl], obj_faces, h, boxes[sl], dims)))
+            common = torch.cat(counts)[:, 0].cpu().numpy()
+        else:
+            common = np.zeros(scenes, np.int64)
+        volumes = torch.stack(volumes).cpu().numpy()
+    cell = (float(h) * float(h)) * float(h)
+    hand_volumes = volumes[0].copy()
+    for k in range(1, hands):
+        hand_volumes = hand_volumes + volumes[k]
+    return {"inter_volumes": (common.astype(np.float64) * cell).tolist(), "hand_volumes": hand_volumes.tolist(),
+            "obj_volumes": volumes[hands].tolist()}

@@ -422,6 +422,36 @@ int hm_threshold_counts(const void* dist, long n, int is_f64, const double* val_
 int hm_fscore(const float* x_d2, const float* y_d2, int B, int N, int M, const float* thresholds, int T, double* out,
               hipStream_t stream);
 
+/* ------------------------------------------------------------------ solid voxels, overlap counts, mesh volume (csrc/solidvox.hip)
+ * The hand-object intersection volume of the ObMan protocol.  Not in the reference tree: the rules below ARE the definition
+ * (DESIGN.md section 7), pinned bit for bit by the fp32 NumPy restatement of tests/volmetrics_ref.py.
+ *
+ * Lattice: world-anchored, pitch h (fp32); the centre of voxel index i on any axis is ((float)i + 0.5f) * h, i may be negative.
+ * Inside test: the rule of csrc/sdf.hip (csrc/inside_test.h).  Row (j, k) with centre (cy, cz) tests a triangle only if cy and
+ * cz lie in the closed fp32 [min, max] of its three vertices' y and z; ray_x_crosses(cy, cz, ...) then gives xhit, every
+ * operation fp32 IEEE without contraction; voxel i of the row is inside iff the number of crossings with xhit > centre(i),
+ * strictly, is odd.  A face that names a vertex outside [0, V) is skipped.
+ *
+ * hm_solid_voxels: verts (B,V,3) fp32 and faces (F,3) int32 on the device; boxes: HOST int[B*6] = {i0, j0, k0, nx, ny, nz} per
+ * frame, read during the call and copied, on `stream`, into the caller's device buffer boxes_dev (B*6 ints), which the kernels
+ * read (pageable memory: stream-ordered, not capturable in a hipGraph).  words (B, NZ, NY, NWX) uint32 on the device: bit t of
+ * word w in row (k, j) of frame b is voxel (i0 + 32w + t, j0 + j, k0 + k); every bit outside the frame's own nx, ny, nz is 0;
+ * an empty box (an extent of 0) gives zeros.  The call clears `words` itself.  Two calls return the same bits, a frame does not
+ * depend on the others, and a voxel does not depend on the box that asked for it.
+ * HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: B, V or F < 1, a NULL pointer, a pitch that is not finite and positive,
+ * a negative dimension or extent, nx > 32 * NWX, ny > NY, nz > NZ, an index outside [-2^22, 2^22]. */
+int hm_solid_voxels(const float* verts, const int* faces, int B, int V, int F, float pitch, const int* boxes, int NWX, int NY,
+                    int NZ, int* boxes_dev, void* words, hipStream_t stream);
+/* a (a_sets, B, words_per_frame) and b (B, words_per_frame) uint32 on the device -> counts (B,3) unsigned 64-bit integers
+ * {popcount(A & b), popcount(A), popcount(b)} per frame with A the OR of the a_sets arrays of a: two hands are voxelised
+ * separately and OR-ed, since parity over a merged mesh would cancel where the hands overlap each other.
+ * words_per_frame == 0 is HM_OK, all zero. */
+int hm_voxel_overlap(const void* a, int a_sets, const void* b, int B, long words_per_frame, void* counts, hipStream_t stream);
+/* out[b] = |sum_f det(p1 - r, p2 - r, p3 - r)| / 6 with r the frame's vertex 0: differences and determinant in double from the
+ * fp32 vertices; thread t of the frame's 256-thread workgroup sums the faces t, t + 256, ... in that order and the 256 sums are
+ * folded by a halving tree (s[t] += s[t + w], w = 128 ... 1): the same bits on every call and at every batch position. */
+int hm_mesh_volume(const float* verts, const int* faces, int B, int V, int F, double* out, hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
