@@ -215,7 +215,7 @@ __device__ __forceinline__ void sil_reduce_frame(int b, const float* __restrict_
 
 // ---------------------------------------------------------------- records of the backward's work list (raster_lines.hip builds it, raster_sweep.hip walks it)
 struct SweepFace {            // 64 B: one face of the flattened work list
-    int bf, b, off, flags;    // face slot b*F+fi, frame, first item, bit 0: accumulate with atomics (capacity overflow)
+    int bf, b, off, spare;    // face slot b*F+fi, frame, first item, unused (keeps the record at 64 bytes)
     float px[3], py[3];       // pixel-space corners (px[0..2], py[0..2] contiguous)
     unsigned short cum[12];   // inclusive item counts of the families, family = winding*6 + edge*2 + axis
 };

@@ -66,17 +66,16 @@ __global__ __launch_bounds__(256) void k_bwd_masks(const float* __restrict__ gin
 //    table of 64-byte records {pixel-space corners, cumulative item counts of the 12 (winding, edge, axis) families}
 //    laid end to end in one global item space (block scan + one 64-bit atomic per block for the block's base: table
 //    order == item order).  Faces that own nothing get their zero gradient written there and never reach the sweep.
-//  * a UNIT is 64 consecutive items = one wave-iteration of k_bwd_sweep, whichever faces they belong to (typically
-//    1-3; a large face spreads over several units, i.e. over several waves).  `ufirst[u]` names the face holding
-//    item 64u.  Every lane rebuilds its item from its face's record in LDS; nothing is wave-serial.
+//  * a UNIT is SWEEP_UNIT (256) consecutive items, walked by one wave of k_bwd_sweep in trips of 64, whichever faces they
+//    belong to (a large face spreads over several units, i.e. over several waves; SWEEP_PASS_FACES faces of a unit are staged at
+//    a time).  `ufirst[u]` names the face holding the unit's first item.  Every lane rebuilds its item from its face's record in LDS; nothing is wave-serial.
 //  * an item resolves its two sweeps to slices of per-line source arrays (k_bwd_lines); the pairs of the 64 items are
 //    flattened over the wave: pair p goes to lane p % 64, which finds its item by a binary search of the items'
 //    exclusive pair counts in LDS (pairs per item are heavy-tailed: mean 5, lines tangent to the band hold hundreds).
-//  * a lane keeps running sums while its pairs stay on one (face, corner) target and flushes them into the face's six
-//    LDS accumulators when the target changes.  A face inside one unit is stored directly; a face cut by one unit
-//    boundary is added by its two units with hardware float atomics onto a zeroed target (commutative: deterministic);
-//    a face spread over three or more units leaves per-unit partials and the unit that draws the last ticket adds them
-//    in unit order (deterministic).
+//  * a lane keeps running sums (doubles) while its pairs stay on one (face, corner) target and flushes them into the face's
+//    six LDS accumulators when the target changes.  Every addend is rounded to the sum grid first (hm_quant), so the sums
+//    are exact and do not depend on their order: a face inside one unit is stored directly; a face cut by unit boundaries -
+//    one or many - is added by each of its units with hardware double atomics onto the target the compaction zeroed.
 // parts (B,F,3 mesh corners,2): d/d(x, y) of the NDC face vertices.
 
 // item count of the (edge, axis) line family between end points with sweep-axis coordinates a0, a1
@@ -182,9 +181,8 @@ __device__ __forceinline__ void sweep_compact(int blk, int nblk, int fpt, const 
             SweepFace rec;
             const int nn = sweep_face_record(bf, faces9, boxes, owned, F, is, rec);
             const int u_lo = off >> SWEEP_USHIFT, u_hi = (off + nn - 1) >> SWEEP_USHIFT;
-            const bool over = u_hi >= sl.ucap || u_hi + idx >= sl.slot_cap;
             rec.off = off;
-            rec.flags = over ? 1 : 0;
+            rec.spare = 0;
             zero = u_hi > u_lo;                                  // accumulated with double atomics by its units
             const uint4* r4 = reinterpret_cast<const uint4*>(&rec);
             uint4* t4 = reinterpret_cast<uint4*>(sl.tab + idx);

@@ -6,9 +6,22 @@
 __device__ __forceinline__ void project_vertex(const float* __restrict__ p, const float* __restrict__ k, float orig_size,
                                                float* out)
 {
-    const float x = p[0], y = p[1], z = p[2];
+    // nr.projection's camera transform with R = identity, t = 0, written out as oracle/nmr.py does: nothing changes but a
+    // non-finite coordinate, which 0 * inf / 0 * NaN spread to the vertex's other coordinates
+    const float x = ((p[0] + p[1] * 0.0f) + p[2] * 0.0f) + 0.0f;
+    const float y = ((p[0] * 0.0f + p[1]) + p[2] * 0.0f) + 0.0f;
+    const float z = ((p[0] * 0.0f + p[1] * 0.0f) + p[2]) + 0.0f;
     const float zz = z + 1e-9f;
-    const float xn = x / zz, yn = y / zz;
+    float xn = x / zz, yn = y / zz;
+    // The distortion polynomial with all-zero coefficients is the identity, except where it is not: nr.projection (and
+    // oracle/nmr.py) multiply the zeros with r^2, r^4, r^6 of the normalised point and 0 * inf is NaN.  A point whose r^6
+    // overflows (beyond ~2.6e6 image-plane units: a vertex within a hair of the camera plane) or that is not finite projects to
+    // NaN there, and its faces are culled; the same here - such a face used to be rasterised as a sliver across the screen.
+    {
+        const float r2 = xn * xn + yn * yn;
+        const float r6 = (r2 * r2) * r2;
+        if (!(r6 <= 3.402823466e38f)) xn = yn = __builtin_nanf("");
+    }
     float u = xn * k[0] + yn * k[1];
     u = u + k[2];
     float v = xn * k[3] + yn * k[4];

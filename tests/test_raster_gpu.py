@@ -217,9 +217,9 @@ def test_no_antialiasing_render_and_gradient_match_oracle(obj):
 @pytest.mark.parametrize("obj", ["bottle", "cube"])
 def test_sweep_scheduling_and_capacity_paths_do_not_change_the_gradient(obj):
     """The edge sweeps' results must not depend on scheduling: the number of persistent workgroups (hm_tune_sweep_blocks)
-    leaves the gradient bit-identical, and with the capacity tables of the work list shrunk to a handful of entries
-    (hm_debug_sweep_caps: binary search for a unit's first face, faces accumulated with float atomics) it still matches
-    to summation order."""
+    leaves the gradient bit-identical, and so do the capacity tables of the work list shrunk to a handful of entries
+    (hm_debug_sweep_caps: binary search for a unit's first face) - the sweeps add exact sums with double atomics, so no
+    order of the units shows in a bit."""
     from homan_amd import lib as hlib
     from homan_amd import ops
     L = hlib.lib()
@@ -244,10 +244,8 @@ def test_sweep_scheduling_and_capacity_paths_do_not_change_the_gradient(obj):
     assert ref.abs().max() > 0
     for blocks in (8, 64, 768):
         assert torch.equal(grad(blocks=blocks), ref), blocks
-    scale = ref.abs().max()
     for cap in (1, 3, 40):
-        np.testing.assert_allclose((grad(cap=cap) / scale).cpu().numpy(), (ref / scale).cpu().numpy(), atol=2e-6,
-                                   err_msg=f"cap {cap}")
+        assert torch.equal(grad(cap=cap), ref), cap
 
 
 def test_large_batches_take_the_four_faces_per_thread_work_list():
