@@ -210,6 +210,32 @@ def evaluate_sequence_plausibility(seq_res, frame_nb, obj_faces, mano_faces_clos
     return res
 
 
+def evaluate_sequence_surface(seq_res, frame_nb, obj_faces, mano_faces_closed, chunk=512, contact_thresh=0.005):
+    """Surface-distance plausibility of every interpolated frame of one sequence (`pointmetrics.get_surface_metrics`); no ground
+    truth is needed.  seq_res, obj_faces, mano_faces_closed and chunk as `evaluate_sequence_plausibility` (the frames are
+    interpolated and flipped the same way) -> per-frame float64 arrays "pen_depth" (hand into object, to the object's surface),
+    "pen_depth_obj" (object vertices inside the hand), "min_dist", "contact_share" (hand vertices within `contact_thresh` of
+    the surface or inside it) and "has_contact" (0 / 1), and their means over the frames under the same names with "_mean".
+    A frame's values do not depend on the chunk size."""
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    if not (np.isfinite(float(contact_thresh)) and float(contact_thresh) >= 0):
+        raise ValueError(f"contact_thresh must be finite and not negative, got {contact_thresh}")
+    obj = interpolate_sequence(seq_res, frame_nb, "obj_verts3d", CAMEXTR_SIGNS)
+    verts = interpolate_sequence(seq_res, frame_nb, "hand_verts3d", CAMEXTR_SIGNS)
+    hand_faces, object_faces = _faces(mano_faces_closed), _faces(obj_faces)
+    keys = ("pen_depth", "pen_depth_obj", "min_dist", "contact_share", "has_contact")
+    lists = {key: [] for key in keys}
+    for f0 in range(0, frame_nb, chunk):
+        part = pointmetrics.get_surface_metrics(verts[f0:f0 + chunk], obj[f0:f0 + chunk], hand_faces, object_faces,
+                                                contact_thresh=contact_thresh)
+        for key in keys:
+            lists[key] += part[key]
+    res = {key: np.asarray(lists[key], np.float64) for key in keys}
+    res.update({f"{key}_mean": float(vals.mean()) for key, vals in list(res.items())})
+    return res
+
+
 PROTOCOL_KEYS = ("joint_err", "joint_err_al", "joint_err_sc_tr", "mesh_err", "mesh_err_al", "f@5", "f@15", "f_al@5", "f_al@15")
 
 

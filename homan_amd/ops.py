@@ -1163,3 +1163,44 @@ def voxel_overlap(a, b):
     _lib.check(_lib.lib().hm_voxel_overlap(_lib.ptr(a) if per_frame else None, sets, _lib.ptr(b) if per_frame else None, B,
                                            per_frame, _lib.ptr(counts), _lib.stream()), "hm_voxel_overlap")
     return counts
+
+
+SURFDIST_CHUNK = 256             # faces staged through LDS per pass (SD_CHUNK of csrc/surfdist.hip)
+
+
+def point_mesh_distance(points, verts, faces, closest=False):
+    """Exact distance of points (B,N,3) to the triangle meshes verts (B,V,3), faces (F,3) - one topology for all frames - and
+    the inside-outside sign (no grad; csrc/surfdist.hip, the rules in include/homan_amd.h) -> {"d2" (B,N) fp32 squared
+    distance to the nearest face, "face" (B,N) int32 the lowest face that attains it, "inside" (B,N) int32 0 / 1: odd number of
+    faces crossed by the +x ray (meaningful for a closed mesh)} and, with closest, {"closest" (B,N,3) fp32}.  A face that
+    names a vertex outside [0, V) or has a non-finite coordinate is skipped; a non-finite point gets (+inf, -1, 0, 0).  The
+    inputs are moved to the GPU as contiguous fp32 / int32; there is no CPU path."""
+    for name, t in (("points", points), ("verts", verts)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError(f"{name}: expected a float tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name}: expected a non-empty (B, N, 3) tensor, got {tuple(t.shape)}")
+    if points.shape[0] != verts.shape[0]:
+        raise ValueError(f"batch sizes differ: {points.shape[0]} vs {verts.shape[0]}")
+    faces = faces.detach() if isinstance(faces, torch.Tensor) else torch.from_numpy(np.array(faces))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError(f"faces: expected a non-empty integer (F, 3) array, got {faces.dtype} {tuple(faces.shape)}")
+    if not torch.cuda.is_available():
+        raise _lib.HomanAmdError("homan_amd.ops.point_mesh_distance needs the GPU (there is no CPU fallback)")
+    dev = next((t.device for t in (points, verts) if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    points = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+    verts = verts.detach().to(device=dev, dtype=torch.float32).contiguous()
+    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
+    B, N, V, F = points.shape[0], points.shape[1], verts.shape[1], faces.shape[0]
+    with torch.cuda.device(dev):
+        out = {"d2": torch.empty(B, N, device=dev), "face": torch.empty(B, N, dtype=torch.int32, device=dev),
+               "inside": torch.empty(B, N, dtype=torch.int32, device=dev)}
+        if closest:
+            out["closest"] = torch.empty(B, N, 3, device=dev)
+        nbytes = _lib.lib().hm_point_mesh_workspace_bytes(B, N, F)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        _lib.check(_lib.lib().hm_point_mesh_distance(_lib.ptr(points), _lib.ptr(verts), _lib.ptr(faces), B, N, V, F,
+                                                     _lib.ptr(out["d2"]), _lib.ptr(out["face"]), _lib.ptr(out["inside"]),
+                                                     _lib.ptr(out.get("closest")), _lib.ptr(ws), _lib.stream()),
+                   "hm_point_mesh_distance")
+    return out

@@ -4,7 +4,9 @@
 reference computes with pytorch3d's `chamfer_distance` and scipy's `cKDTree` - run on an exact brute-force nearest-neighbour
 search in both directions (`hm_cloud_metrics`, csrc/pointmetrics.hip) and the alignment statistics of `hm_align_stats`.
 `get_inter_metrics` (:102-124, called by fit_vid_dataset.py:488-493) reads how deep the hand reaches into the object off
-the object's signed-distance grid.  Inputs are torch tensors on any device and of any float dtype; they are moved to the GPU
+the object's signed-distance grid.  `get_volume_metrics` and `get_surface_metrics` are extras beyond the reference (DESIGN.md
+section 7): the intersection volume on a solid voxeliser, and penetration depth / contact measured to the mesh surface on an
+exact point-to-triangle distance.  Inputs are torch tensors on any device and of any float dtype; they are moved to the GPU
 as contiguous fp32, and each call syncs with the host once.  There is no CPU path: without a GPU these functions raise.
 """
 import numpy as np
@@ -197,3 +199,105 @@ def get_volume_metrics(verts_person, verts_object, faces_person, faces_object, v
         hand_volumes = hand_volumes + volumes[k]
     return {"inter_volumes": (common.astype(np.float64) * cell).tolist(), "hand_volumes": hand_volumes.tolist(),
             "obj_volumes": volumes[hands].tolist()}
+
+
+def surface_frame_bytes(hands, hand_verts, obj_verts):
+    """device bytes one frame of `get_surface_metrics` holds at a time: per hand and direction the three per-point outputs of
+    `ops.point_mesh_distance` (d2, face, inside) and its merge words (8 + 4 bytes per point)"""
+    return int(hands) * (int(hand_verts) + int(obj_verts)) * 24
+
+
+def _d2_at_most(dist):
+    """the largest fp32 x with sqrt((double)x) <= dist (dist >= 0, finite): `d2 <= x` in fp32 is then exactly the comparison of
+    the double distance with the threshold"""
+    with np.errstate(over="ignore"):
+        x = np.float32(float(dist) * float(dist))
+    if not np.isfinite(x):
+        x = np.float32(np.finfo(np.float32).max)
+    while x > 0 and np.sqrt(np.float64(x)) > dist:
+        x = np.nextafter(x, np.float32(-np.inf))
+    while x < np.finfo(np.float32).max and np.sqrt(np.float64(np.nextafter(x, np.float32(np.inf)))) <= dist:
+        x = np.nextafter(x, np.float32(np.inf))
+    return float(x)
+
+
+def get_surface_metrics(verts_person, verts_object, faces_person, faces_object, contact_thresh=0.005, per_vertex=False,
+                        max_bytes=256 << 20):
+    """Penetration depth and contact of hand(s) and object measured to the SURFACES (ObMan's definitions), from the exact
+    point-to-triangle distances and the inside-outside sign of `ops.point_mesh_distance` (csrc/surfdist.hip; rules in
+    include/homan_amd.h).  Inputs as `get_volume_metrics`: verts_person (B*hand_nb, Vh, 3) frame-major, verts_object (B, Vo, 3),
+    faces_person (hand_nb, Fh, 3) closed hand faces, faces_object (>=1, Fo, 3).  Distances are sqrt((double)d2).  Lists of B:
+      "pen_depth"      the largest distance to the object's surface over the hand vertices inside the object, 0.0 when none;
+      "pen_depth_obj"  the same for the object's vertices inside a hand: each hand is queried as its own mesh (parity over
+                       merged hands would cancel where they overlap) and the maximum over the hands is taken;
+      "min_dist"       the smallest distance of a hand vertex to the object's surface;
+      "contact_share"  the share of hand vertices with signed distance <= contact_thresh (inside counts), in double;
+      "has_contact"    pen_depth > 0 or pen_depth_obj > 0 or min_dist <= contact_thresh.
+    per_vertex adds "signed_dist" (B*hand_nb, Vh) float64, negative inside: the contact map.  Frames are walked in chunks whose
+    outputs fit `max_bytes`; a frame's values do not depend on the chunking.  The sign needs closed meshes.  No CPU path."""
+    verts_person, verts_object = torch.as_tensor(verts_person), torch.as_tensor(verts_object)
+    _check_clouds(verts_person=verts_person, verts_object=verts_object)
+    thresh = float(contact_thresh)
+    if not (np.isfinite(thresh) and thresh >= 0):
+        raise ValueError(f"contact_thresh must be finite and not negative, got {contact_thresh}")
+    scenes = verts_object.shape[0]
+    hands = verts_person.shape[0] // scenes
+    if hands < 1 or hands > 3 or hands * scenes != verts_person.shape[0]:
+        raise ValueError(f"{verts_person.shape[0]} hands for {scenes} frames")
+    if int(max_bytes) < 1:
+        raise ValueError(f"max_bytes must be positive, got {max_bytes}")
+    faces_person = np.asarray(torch.as_tensor(faces_person).cpu())
+    if faces_person.ndim == 2:
+        faces_person = faces_person[None]
+    obj_faces = np.asarray(torch.as_tensor(faces_object).cpu())
+    obj_faces = obj_faces[0] if obj_faces.ndim == 3 else obj_faces
+    Vh, Vo = verts_person.shape[1], verts_object.shape[1]
+    frame_bytes = surface_frame_bytes(hands, Vh, Vo)
+    if frame_bytes > int(max_bytes):
+        raise ValueError(f"one frame needs {frame_bytes} bytes of per-point outputs; max_bytes is {max_bytes}")
+    person, obj = _on_gpu(verts_person, verts_object)
+    dev = obj.device
+    d2_contact = _d2_at_most(thresh)
+    with torch.cuda.device(dev):
+        hand_faces = [torch.from_numpy(np.ascontiguousarray(faces_person[k % faces_person.shape[0]], dtype=np.int32)).to(dev)
+                      for k in range(hands)]
+        object_faces = torch.from_numpy(np.ascontiguousarray(obj_faces, dtype=np.int32)).to(dev)
+        per_hand = [person.reshape(scenes, hands, Vh, 3)[:, k].contiguous() for k in range(hands)]
+        chunk = max(int(max_bytes) // frame_bytes, 1)
+        rows, d2_maps, in_maps = [], [], []
+        for f0 in range(0, scenes, chunk):
+            sl = slice(f0, min(f0 + chunk, scenes))
+            n = sl.stop - sl.start
+            deep = torch.zeros(n, device=dev)                         # largest d2 of a hand vertex inside the object
+            deep_obj = torch.zeros(n, device=dev)
+            near = torch.full((n,), float("inf"), device=dev)         # smallest d2 of a hand vertex
+            touching = torch.zeros(n, dtype=torch.int64, device=dev)
+            chunk_d2, chunk_in = [], []
+            for k in range(hands):
+                to_obj = ops.point_mesh_distance(per_hand[k][sl], obj[sl], object_faces)
+                inside = to_obj["inside"] == 1
+                deep = torch.maximum(deep, torch.where(inside, to_obj["d2"], torch.zeros_like(to_obj["d2"])).amax(1))
+                near = torch.minimum(near, to_obj["d2"].amin(1))
+                touching += (inside | (to_obj["d2"] <= d2_contact)).sum(1)
+                chunk_d2.append(to_obj["d2"])
+                chunk_in.append(inside)
+                to_hand = ops.point_mesh_distance(obj[sl], per_hand[k][sl], hand_faces[k])
+                deep_obj = torch.maximum(deep_obj, torch.where(to_hand["inside"] == 1, to_hand["d2"],
+                                                               torch.zeros_like(to_hand["d2"])).amax(1))
+            rows.append(torch.stack([deep.double(), deep_obj.double(), near.double(), touching.double()]))
+            if per_vertex:                                            # (frames, hands, Vh): frame-major, as verts_person
+                d2_maps.append(torch.stack(chunk_d2, 1))
+                in_maps.append(torch.stack(chunk_in, 1))
+        table = torch.cat(rows, 1).cpu().numpy()                      # (exact: maxima and minima of fp32 values, counts)
+        if per_vertex:
+            d2_maps, in_maps = torch.cat(d2_maps).cpu().numpy(), torch.cat(in_maps).cpu().numpy()
+    pen, pen_obj, min_dist = (np.sqrt(table[k]) for k in range(3))
+    share = table[3] / np.float64(hands * Vh)
+    res = {"pen_depth": pen.tolist(), "pen_depth_obj": pen_obj.tolist(), "min_dist": min_dist.tolist(),
+           "contact_share": share.tolist(),
+           "has_contact": ((pen > 0) | (pen_obj > 0) | (min_dist <= thresh)).tolist()}
+    if per_vertex:
+        dist = np.sqrt(d2_maps.astype(np.float64))
+        res["signed_dist"] = np.where(in_maps, -dist, dist).reshape(scenes * hands, Vh)
+    return res
+

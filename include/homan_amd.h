@@ -452,6 +452,41 @@ int hm_voxel_overlap(const void* a, int a_sets, const void* b, int B, long words
  * folded by a halving tree (s[t] += s[t + w], w = 128 ... 1): the same bits on every call and at every batch position. */
 int hm_mesh_volume(const float* verts, const int* faces, int B, int V, int F, double* out, hipStream_t stream);
 
+/* ------------------------------------------------------------------ exact point-to-mesh distance and sign (csrc/surfdist.hip)
+ * The surface metrics of homan_amd/pointmetrics.py get_surface_metrics.  Not in the reference tree: the rules below ARE the
+ * definition, pinned bit for bit by the fp32 NumPy restatement of tests/surfmetrics_ref.py.  Every
+ * operation is fp32 IEEE without contraction; a dot product is (x*x + y*y) + z*z.
+ *
+ * points (B,N,3), verts (B,V,3) fp32 and faces (F,3) int32 (one topology for all frames) on the device.  Outputs, each optional
+ * (NULL) but not all four: d2 (B,N) fp32, face_idx (B,N) int32, inside (B,N) int32 0 / 1, closest (B,N,3) fp32.
+ *
+ * Distance to a face (a, b, c), Ericson 5.1.5: ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c; d1 = ab.ap, d2 = ac.ap,
+ * d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp; vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The first region
+ * that holds gives the closest point q:
+ *   A   d1 <= 0 and d2 <= 0                             q = a
+ *   B   d3 >= 0 and d4 <= d3                            q = b
+ *   AB  vc <= 0 and d1 >= 0 and d3 <= 0                 q = a + (d1 / (d1 - d3)) ab
+ *   C   d6 >= 0 and d5 <= d6                            q = c
+ *   AC  vb <= 0 and d2 >= 0 and d6 <= 0                 q = a + (d2 / (d2 - d6)) ac
+ *   BC  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0       q = b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) (c - b)
+ *   interior otherwise: s = (va + vb) + vc              q = (a + (vb / s) ab) + (vc / s) ac
+ * and D = |p - q|^2.  A face whose cross product (ab_y ac_z - ab_z ac_y, ab_z ac_x - ab_x ac_z, ab_x ac_y - ab_y ac_x) is
+ * exactly (0, 0, 0) is its three segments ab, bc, ca: per segment u -> v, t = ((p - u).(v - u)) / |v - u|^2 clamped to [0, 1]
+ * (t = 0 when |v - u|^2 is not positive), q = u + t (v - u); the smallest D wins, ties in the order ab, bc, ca.
+ * Per point: d2 = the minimum of D over the faces, face_idx = the lowest face that attains it, closest = that face's q.
+ * inside = 1 iff the number of faces with ray_x_crosses(p_y, p_z, a, b, c, &xhit) (csrc/inside_test.h, the voxeliser's rule)
+ * and xhit > p_x, strictly, is odd: it means "inside" for a closed mesh only.
+ * A face that names a vertex outside [0, V) or has a non-finite coordinate is skipped for distance and sign.  A non-finite
+ * point, or a mesh whose every face is skipped, gives d2 = +inf, face_idx = -1, inside = 0, closest = 0.
+ * Two calls return the same bits and a frame's values depend neither on B nor on its place in the batch: the minimum and the
+ * parity are merged through integer operations only (csrc/surfdist.hip).  workspace: hm_point_mesh_workspace_bytes(B, N, F)
+ * bytes (0 for batches large enough that the faces of a frame are not split; NULL is then accepted); the call initialises it
+ * on `stream`.  HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: B, N, V or F < 1, a NULL input, all four outputs NULL, a
+ * NULL workspace where bytes are needed.  Every index is a 64-bit product of the int sizes: no size is refused for overflow. */
+size_t hm_point_mesh_workspace_bytes(int B, int N, int F);
+int hm_point_mesh_distance(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, float* d2,
+                           int* face_idx, int* inside, float* closest, void* workspace, hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
