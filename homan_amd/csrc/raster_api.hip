@@ -14,7 +14,7 @@
 //   per-(face,edge,axis) line sweeps comparing in/out alpha (Kato et al. 2018).
 //
 // Design (CDNA4), see DESIGN.md section 4 for the measurements behind each choice:
-//   forward   k_setup_faces (thread / face: optional rigid transform, projection, tight sample box, super-region bins; extra
+//   forward   k_setup_faces (thread / face: optional rigid transform, projection, tight sample box, face bins per region; extra
 //             workgroups write the camera-space vertices) -> k_raster_fwd (workgroup = 32x32-sample region: candidates of
 //             its bin split into the camera-facing winding class and the hidden one; (candidate, 4x4 block) units
 //             flattened over the threads; visibility by ds_min_u64 on an LDS z-buffer = the strict z test in ascending face
@@ -56,9 +56,9 @@ size_t hm_sil_workspace_bytes(int B, int V, int F, int S)
     n += al256((size_t)B * is * (is / 16) * 4); // column masks, 2 planes
     n += al256((size_t)B * F * 24 * 4);         // parts
     n += al256((size_t)B * F * 2);              // owned
-    n += al256((size_t)B * SR_MAX * 8);                        // super-region bin counters + their ticket words
+    n += al256(ws_bin_counter_bytes(B, S));                    // face-bin counters (+ ticket words of super-regions)
     n += al256((size_t)B * (S / 16) * (S / 16));               // per-region "outputs hold the empty pattern" flags
-    n += al256((size_t)B * SR_MAX * F * 4);                    // super-region face lists (worst case: every face in every bin)
+    n += al256(ws_bin_list_bytes(B, F, S));                    // face lists of the bins (worst case: every face in every bin)
     n += al256(4 * (size_t)B * is * (is / 64) * 16);            // per-line records {mask word, sources before it}
     n += al256((size_t)B * 2 * is * 16);                        // per-line summaries {first, last+1, word mask} x 2 planes
     n += al256(4 * (size_t)B * is * is * sizeof(SweepSrc));     // per-line source arrays (2 planes x 2 orientations)
@@ -124,7 +124,7 @@ int hm_sil_fwd_phase_clips(const float* verts, const int* faces, int faces_bstri
     HM_CHECK_ARG(faces_bstride == 0 || faces_bstride == 3 * F);
     SilWs w = carve(workspace, B, V, F, S);
     const int is = 2 * S;
-    int* bins = is <= (SR_MAX == 64 ? 1024 : 0) ? w.bin_cnt : nullptr;      // <= SR_MAX super-regions per frame
+    int* bins = is <= HM_BINS_MAX_IS ? w.bin_cnt : nullptr;      // region bins up to 512^2 samples, super-regions above
     HM_CHECK_ARG(!cam_verts_out || rigid_rot6d);
     if (phases & 1)
         hm_launch_setup_faces(w, verts, K, orig_size, faces, faces_bstride, B, V, F, is, bins, rigid_rot6d, rigid_trans, rigid_scale,
@@ -188,7 +188,7 @@ int hm_sil_fwd_multi(const HmSilRender* renders, int n, int phases, hipStream_t 
         for (int q = 0; q < g; ++q) HM_CHECK_ARG(renders[q].workspace != r.workspace);      // a workspace carries ONE render
         ws[g] = carve(r.workspace, r.B, r.V, r.F, r.S);
         const int is = 2 * r.S;
-        int* bins = is <= (SR_MAX == 64 ? 1024 : 0) ? ws[g].bin_cnt : nullptr;
+        int* bins = is <= HM_BINS_MAX_IS ? ws[g].bin_cnt : nullptr;      // (per render: both bin modes may share the launch)
         const SetupFacesArgs s1 = {r.verts, r.K, r.orig_size, r.faces, r.faces_bstride, r.B, r.V, r.F, is, bins, r.rigid_rot6d,
                                    r.rigid_trans, r.rigid_scale, r.rigid_abs, r.clip_len ? r.clip_len : r.B, r.cam_verts_out};
         sa[g] = s1;
@@ -328,8 +328,8 @@ int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, i
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return HM_ERR_LAUNCH;
     float ms = 0.f;
-    // the forward's last workgroup emptied the super-region bins: fill them again and keep them across the timed launches
-    int* bins = 2 * S <= 1024 ? w.bin_cnt : nullptr;
+    // the forward's workgroups emptied the face bins: fill them again and keep them across the timed launches
+    int* bins = 2 * S <= HM_BINS_MAX_IS ? w.bin_cnt : nullptr;
     hm_launch_setup_faces(w, verts, K, 1.0f, faces, 0, B, V, F, 2 * S, bins, nullptr, nullptr, nullptr, 0, B, nullptr, stream);
     // (steady state of a fixed loop: background regions skipped; the bins are not reset between the launches)
     RasterFwdArgs a = {B, F, S, 0.1f, 100.0f, pooled, keep, ref, true, work_order, nullptr, bins, 0, 1, nullptr, 0, false, false, 0};
@@ -339,7 +339,7 @@ int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, i
     (void)hipEventSynchronize(e1);
     (void)hipEventElapsedTime(&ms, e0, e1);
     avg_ms[0] = ms / (float)reps;
-    (void)hipMemsetAsync(w.bin_cnt, 0, (size_t)B * SR_MAX * 4, stream);
+    if (bins) (void)hipMemsetAsync(w.bin_cnt, 0, (size_t)B * ws_bins(S) * 4, stream);
     (void)hipEventRecord(e0, stream);
     for (int i = 0; i < reps; ++i) hm_launch_sweep(w, B, F, S, 1e-3f, 0, stream);
     (void)hipEventRecord(e1, stream);
@@ -428,6 +428,12 @@ int hm_sil_read_boxes(const void* workspace, int B, int V, int F, int S, void* o
 {
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.boxes, (size_t)B * F * 8, hipMemcpyDeviceToDevice, stream) == hipSuccess ? HM_OK
+                                                                                                         : HM_ERR_LAUNCH;
+}
+int hm_sil_read_owned(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream)
+{
+    SilWs w = carve((void*)workspace, B, V, F, S);
+    return hipMemcpyAsync(out, w.owned, (size_t)B * F * 2, hipMemcpyDeviceToDevice, stream) == hipSuccess ? HM_OK
                                                                                                          : HM_ERR_LAUNCH;
 }
 int hm_sil_read_faces9(const void* workspace, int B, int V, int F, int S, float* out, hipStream_t stream)

@@ -64,11 +64,28 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-#define SR_MAX 64          // super-regions per frame (is <= 1024)
-// log2 of the super-region side in samples: 64^2 up to 512^2 samples, 128^2 above -> at most 8 x 8 = SR_MAX bins.  A
-// region workgroup scans its whole bin, so a bin holds 4 (is <= 512) or 16 regions' worth of faces: the finer bins cut
-// the scan of the 512^2 rasters by 4 (k_raster_fwd 63.5 -> 60.1 us).
-__host__ __device__ __forceinline__ int hm_sr_shift(int is) { return is <= 512 ? 6 : 7; }
+// Face bins of a frame (k_setup_faces fills them, k_raster_fwd reads them).  Two modes, chosen by the render size alone:
+//   region bins (is <= 512): one bin per 32x32-sample region = per raster workgroup, at most 16 x 16 = RB_MAX per frame.  Sample x
+//     lies in bin column x >> 5, sample y in bin row y >> 5 (the region row is/32 - 1 - (y >> 5): the outputs are flipped).  The
+//     list of a bin IS the candidate set of its workgroup: an entry is face | winding mask << 30 (2F < 2^30), so the raster's
+//     scan loads neither the face's box nor tests it, and a bin has ONE reader, which empties the count itself - no ticket.
+//   super-regions (512 < is <= 1024): bins of 128x128 samples, at most 8 x 8 = SR_MAX per frame, shared by 16 region workgroups
+//     that each test the listed faces' boxes against their own region and draw a ticket so that the last one empties the
+//     count.  (Region bins there would be 1024 lists of F entries per frame.)
+// Every refinement of the bins has paid: whole frame -> super-regions 85 -> 74 us, 128^2 -> 64^2 bins below 512^2 samples
+// 63.5 -> 60.1 us ("the finer bins cut the scan by 4"); region bins are the end of that road.
+#define SR_MAX 64          // super-regions per frame (512 < is <= 1024)
+#define RB_MAX 256         // region bins per frame (is <= 512)
+#define HM_BINS_MAX_IS 1024      // larger renders have no bins: a workgroup scans the whole frame
+__host__ __device__ __forceinline__ bool hm_region_bins(int is) { return is <= 512; }
+// log2 of the bin side in samples
+__host__ __device__ __forceinline__ int hm_sr_shift(int is) { return hm_region_bins(is) ? 5 : 7; }
+// bins per side / per frame of a render with bins (`is` is a multiple of 32)
+__host__ __device__ __forceinline__ int hm_bins_per_side(int is) { return (is + (1 << hm_sr_shift(is)) - 1) >> hm_sr_shift(is); }
+__host__ __device__ __forceinline__ int hm_bins_per_frame(int is)
+{
+    return is <= HM_BINS_MAX_IS ? hm_bins_per_side(is) * hm_bins_per_side(is) : 0;
+}
 
 __device__ __forceinline__ int hm_wave_scan_incl(int v)
 {

@@ -3,8 +3,9 @@
 
 // ---------------------------------------------------------------- forward raster
 // Workgroup = 4 wavefronts = one 32x32-sample region (a 2x2 block of 8x8-pixel output tiles) of one frame.
-//   1. binning on the fly: the workgroup scans the 8-byte screen boxes of the frame (coalesced) and keeps the
-//      (face, winding) entries overlapping its region in an LDS candidate list;
+//   1. candidates: up to 512^2 samples the face setup has binned the faces per region, and the workgroup copies the (face,
+//      winding mask) entries of its own bin into an LDS candidate list, split by winding class; above, it scans the faces of its
+//      super-region (or of the whole frame), loads their 8-byte screen boxes and keeps those overlapping its region;
 //   2. one thread per candidate builds the face record (edge vectors, reciprocal depths, barycentric inverse) in LDS
 //      and counts the 4x4-sample blocks of (face box & region);
 //   3. the (candidate, block) units of the pass are FLATTENED over the 256 threads (unit u -> candidate by a binary
@@ -97,8 +98,10 @@ __device__ __forceinline__ void raster_fwd_body(
 
     int had_any = 0;       // block-uniform: some face overlaps this region
     const uint2* bx = reinterpret_cast<const uint2*>(boxes) + (long)b * F;
-    // faces to scan: the bin of this region's super-region (or the whole frame without bins)
-    const int nsx = (is + (1 << hm_sr_shift(is)) - 1) >> hm_sr_shift(is);
+    // faces to scan: this region's own bin (region bins: the list is the candidate set), the bin of its super-region, or the
+    // whole frame without bins
+    const bool own_bin = bin_cnt && hm_region_bins(is);
+    const int nsx = hm_bins_per_side(is);
     const int sr = (gy0 >> hm_sr_shift(is)) * nsx + (gx0 >> hm_sr_shift(is));
     // the two words every workgroup needs first, requested together: the size of its bin and the state of its outputs
     unsigned char* rstate = region_state + (long)b * regions_x * regions_x + region;
@@ -106,7 +109,8 @@ __device__ __forceinline__ void raster_fwd_body(
     const int rstate0 = persistent ? (int)*rstate : 0;
     const int* scan = bin_cnt ? bin_list + ((long)b * nsx * nsx + sr) * F : nullptr;
     // An empty bin in front of outputs that already hold the empty pattern: nothing to rasterise, nothing to write (~60 %
-    // of the workgroups of a clip, every iteration) - leave before touching LDS.  (The bin ticket still has to be drawn.)
+    // of the workgroups of a clip, every iteration) - leave before touching LDS.  (A super-region's ticket still has to be
+    // drawn; a region bin has no ticket, and "empty bin" there is "no face touches this region".)
     const bool idle = nscan == 0 && rstate0 == 1;
     const bool ts_on = hm_ts_enabled(hint) && tid == 0;
     if (ts_on) hm_ts_store(ts_slots, blk, 0, ts_t0);
@@ -234,20 +238,40 @@ __device__ __forceinline__ void raster_fwd_body(
     for (int cbase = 0; cbase < nscan; cbase += CAND_CAP) {
         if (tid == 0) { cand_n[0] = 0; cand_n[1] = 0; }
         __syncthreads();
-        uint2 v[CAND_CAP / 256];
+        // A region bin has one reader, this workgroup: it empties the count for the next forward once it holds it (the list
+        // stays as it is).  Behind the barrier: every wave loads the count for itself and has needed it to get here; a store
+        // in front of the barrier could reach memory before a later wave's load and leave the waves with different counts.
+        if (own_bin && reset_bins && cbase == 0 && tid == 0) bin_cnt[b * nsx * nsx + sr] = 0;
         int vf[CAND_CAP / 256];
+        unsigned vm[CAND_CAP / 256];
+        if (own_bin) {
+            // entries of the own bin: face | winding mask << 30, every one a candidate (0 = no entry: the mask is never 0)
 #pragma unroll
-        for (int k = 0; k < CAND_CAP / 256; ++k) {
-            const int e = cbase + k * 256 + tid;
-            vf[k] = e < nscan ? (scan ? scan[e] : e) : -1;
+            for (int k = 0; k < CAND_CAP / 256; ++k) {
+                const int e = cbase + k * 256 + tid;
+                const unsigned ent = e < nscan ? (unsigned)scan[e] : 0u;
+                vf[k] = (int)(ent & 0x3fffffffu);
+                vm[k] = ent >> 30;
+            }
+        } else {
+            uint2 v[CAND_CAP / 256];
+#pragma unroll
+            for (int k = 0; k < CAND_CAP / 256; ++k) {
+                const int e = cbase + k * 256 + tid;
+                vf[k] = e < nscan ? (scan ? scan[e] : e) : -1;
+            }
+#pragma unroll
+            for (int k = 0; k < CAND_CAP / 256; ++k) v[k] = vf[k] >= 0 ? bx[vf[k]] : make_uint2(0u, 0u);
+#pragma unroll
+            for (int k = 0; k < CAND_CAP / 256; ++k) {
+                const int x0 = v[k].x & 0x3fff, y0 = (int)(v[k].x >> 16), x1 = (int)(v[k].y & 0xffff), y1 = (int)(v[k].y >> 16);
+                vm[k] = (x1 < gx0 || x0 > gx1 || y1 < gy0 || y0 > gy1) ? 0u : ((v[k].x >> 14) & 3u);
+            }
         }
-#pragma unroll
-        for (int k = 0; k < CAND_CAP / 256; ++k) v[k] = vf[k] >= 0 ? bx[vf[k]] : make_uint2(0u, 0u);
 #pragma unroll
         for (int k = 0; k < CAND_CAP / 256; ++k) {
             const int fi = vf[k];
-            const int x0 = v[k].x & 0x3fff, y0 = (int)(v[k].x >> 16), x1 = (int)(v[k].y & 0xffff), y1 = (int)(v[k].y >> 16);
-            const unsigned m = (x1 < gx0 || x0 > gx1 || y1 < gy0 || y0 > gy1) ? 0u : ((v[k].x >> 14) & 3u);
+            const unsigned m = vm[k];
 #pragma unroll
             for (int var = 0; var < 2; ++var) {
                 const bool hit = (m >> var) & 1u;
@@ -419,10 +443,10 @@ __device__ __forceinline__ void raster_fwd_body(
         }
     }
     __syncthreads();
-    // the last of the (4 or 16) workgroups that read a bin empties it for the next forward.  One ticket word per bin:
-    // returning atomics on a single word from all 7680 workgroups serialise (measured +43 us on the launch).  (Drawing the
+    // super-regions: the last of the 16 workgroups that read a bin empties it for the next forward.  One ticket word per bin:
+    // returning atomics on a single word from all workgroups serialise (measured +43 us on the launch).  (Drawing the
     // ticket right after the scan and using the answer at the very end was measured: k_raster_fwd 51.8 -> 55.5 us.)
-    if (tid == 0 && bin_cnt && reset_bins) {
+    if (tid == 0 && bin_cnt && reset_bins && !own_bin) {
         const int per_side = (1 << hm_sr_shift(is)) / (2 * HM_STILE);
         const int rw = min(per_side, regions_x - per_side * (gx0 >> hm_sr_shift(is))), rh = min(per_side, regions_x - per_side * (gy0 >> hm_sr_shift(is)));
         const int slot = b * nsx * nsx + sr;
@@ -440,6 +464,15 @@ __device__ __forceinline__ void raster_fwd_body(
         if (tid == 0) atomicAdd(&g_raster_ph[7], 1ull);
 #endif
         if (wg_cost && tid == 0) wg_cost[blk] = 0u;
+#ifdef RASTER_TRACE
+        // a workgroup that scanned a list, kept no candidate and leaves here: its scan time alone ([7] = [8] = 0)
+        if (tid == 0 && nscan > 0 && blk < RASTER_TRACE_WGS && (g_raster_trace_F == 0 || g_raster_trace_F == F) &&
+            (g_raster_trace_depth < 0 || g_raster_trace_depth == (pooled_depth ? 1 : 0))) {
+            unsigned* o = g_raster_trace[blk];
+            for (int k = 0; k < 6; ++k) o[k] = rtr[k];
+            o[6] = (unsigned)ts_t0; o[7] = 0u; o[8] = 0u;
+        }
+#endif
         return;
     }
     __syncthreads();          // every thread has read the state before thread 0 rewrites it below

@@ -1,4 +1,4 @@
-// raster_setup.hip -- face setup of the silhouette rasteriser (projection, sample boxes, super-region bins)
+// raster_setup.hip -- face setup of the silhouette rasteriser (projection, sample boxes, face bins)
 #include "raster_ws.h"
 
 // ---------------------------------------------------------------- projection (nr.projection, zero distortion)
@@ -35,10 +35,11 @@ __device__ __forceinline__ void project_vertex(const float* __restrict__ p, cons
 // ---------------------------------------------------------------- face setup
 // projects the three vertices of every face (a vertex is shared by ~6 faces: re-projecting it is cheaper than a
 // separate projection launch on the critical path), packs the (B,F,3,3) NDC face buffer and the 8-byte screen boxes.
-// It also bins the faces into super-regions of 64x64 or 128x128 samples (hm_sr_shift) (counts aggregated per workgroup in LDS, one global atomic per
-// (workgroup, bin)): a raster workgroup then scans the faces of its super-region instead of the whole frame.  The order
-// inside a bin is arbitrary; the raster resolves visibility with a min, so its result does not depend on it.
-// grid (ceil(F/256), B).  bin_cnt must be zero on entry (the raster's last workgroup resets it).
+// It also bins the faces (raster_common.h: region bins of 32x32 samples up to 512^2 samples, super-regions of 128x128 above):
+// counts aggregated per workgroup in LDS, one global atomic per (workgroup, bin).  A raster workgroup then reads the faces of
+// its own region (region bins) or scans those of its super-region instead of the whole frame.  The order inside a bin is
+// arbitrary; the raster resolves visibility with a min, so its result does not depend on it.
+// grid (ceil(F/256), B).  bin_cnt must be zero on entry (the bin's reader - its last reader, for a super-region - resets it).
 // (body: bx / by = the workgroup's block index within its render / its frame; every argument is workgroup-uniform)
 __device__ __forceinline__ void setup_faces_body(const int bx, const int by, const float* __restrict__ verts, const float* __restrict__ K,
                                                      float orig_size, const int* __restrict__ faces, int faces_bstride,
@@ -51,7 +52,7 @@ __device__ __forceinline__ void setup_faces_body(const int bx, const int by, con
                                                      float* __restrict__ cam_out, int nfb)
 {
     HM_STAMP_START(0);
-    __shared__ int s_cnt[SR_MAX], s_base[SR_MAX];
+    __shared__ int s_cnt[RB_MAX], s_base[RB_MAX];
     __shared__ float s_R[9];
     // optional rigid transform of mesh-space `verts` (same arithmetic as hm_rigid_fwd, so the camera-space vertices the
     // other losses get from that entry point are the very numbers rasterised here): the silhouette chain then does not
@@ -77,8 +78,8 @@ __device__ __forceinline__ void setup_faces_body(const int bx, const int by, con
     }
     const int b = by, fi = bx * blockDim.x + threadIdx.x;
     const bool valid = fi < F;
-    const int nsx = (is + (1 << hm_sr_shift(is)) - 1) >> hm_sr_shift(is), nsr = nsx * nsx;
-    if (threadIdx.x < SR_MAX) s_cnt[threadIdx.x] = 0;
+    const int nsx = hm_bins_per_side(is), nsr = nsx * nsx;
+    if (threadIdx.x < RB_MAX) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     unsigned mask = 0;
     int x0 = 1, y0 = 1, x1 = 0, y1 = 0;
@@ -135,30 +136,55 @@ __device__ __forceinline__ void setup_faces_body(const int bx, const int by, con
         boxes[i] = bx;
     }
     if (!bin_cnt) return;
-    // local slots in LDS, one global reservation per (workgroup, bin)
-    const int sx0 = x0 >> hm_sr_shift(is), sx1 = x1 >> hm_sr_shift(is), sy0 = y0 >> hm_sr_shift(is), sy1 = y1 >> hm_sr_shift(is);
-    int local[4];                       // a face larger than 2x2 super-regions reserves its further bins one by one
-    int nloc = 0;
-    if (mask)
-        for (int sy = sy0; sy <= sy1; ++sy)
-            for (int sx = sx0; sx <= sx1; ++sx) {
-                if (nloc < 4) local[nloc] = atomicAdd(&s_cnt[sy * nsx + sx], 1);
-                ++nloc;
-            }
-    __syncthreads();
-    if (threadIdx.x < nsr) {
-        const int c = s_cnt[threadIdx.x];
-        s_base[threadIdx.x] = c ? atomicAdd(&bin_cnt[b * nsr + threadIdx.x], c) : 0;
-    }
-    __syncthreads();
-    if (mask) {
-        int q = 0;
-        for (int sy = sy0; sy <= sy1; ++sy)
-            for (int sx = sx0; sx <= sx1; ++sx, ++q) {
-                const int sr = sy * nsx + sx;
-                const int at = q < 4 ? s_base[sr] + local[q] : atomicAdd(&bin_cnt[b * nsr + sr], 1);
-                bin_list[((long)b * nsr + sr) * F + at] = fi;
-            }
+    const int sh = hm_sr_shift(is);
+    if (hm_region_bins(is)) {
+        // region bins: the face goes into every bin its box touches - columns x0 >> 5 .. x1 >> 5, rows y0 >> 5 .. y1 >> 5, which
+        // is the raster's own overlap test (x1 < gx0 || x0 > gx1 || y1 < gy0 || y0 > gy1) against the bin's 32x32 box, on the
+        // same integer box - a quad across a 512^2 render into all 256.  Counted per bin in LDS, reserved once per
+        // (workgroup, bin); the fill pass places the entries by counting the reserved base up, again in LDS.
+        const int cx0 = x0 >> sh, cx1 = x1 >> sh, cy0 = y0 >> sh, cy1 = y1 >> sh;
+        if (mask)
+            for (int cy = cy0; cy <= cy1; ++cy)
+                for (int cx = cx0; cx <= cx1; ++cx) atomicAdd(&s_cnt[cy * nsx + cx], 1);
+        __syncthreads();
+        if (threadIdx.x < nsr) {
+            const int c = s_cnt[threadIdx.x];
+            s_base[threadIdx.x] = c ? atomicAdd(&bin_cnt[b * nsr + threadIdx.x], c) : 0;
+        }
+        __syncthreads();
+        if (mask)
+            for (int cy = cy0; cy <= cy1; ++cy)
+                for (int cx = cx0; cx <= cx1; ++cx) {
+                    const int bin = cy * nsx + cx;
+                    const int at = atomicAdd(&s_base[bin], 1);
+                    bin_list[((long)b * nsr + bin) * F + at] = (int)((unsigned)fi | (mask << 30));
+                }
+    } else {
+        // local slots in LDS, one global reservation per (workgroup, bin)
+        const int sx0 = x0 >> sh, sx1 = x1 >> sh, sy0 = y0 >> sh, sy1 = y1 >> sh;
+        int local[4];                       // a face larger than 2x2 super-regions reserves its further bins one by one
+        int nloc = 0;
+        if (mask)
+            for (int sy = sy0; sy <= sy1; ++sy)
+                for (int sx = sx0; sx <= sx1; ++sx) {
+                    if (nloc < 4) local[nloc] = atomicAdd(&s_cnt[sy * nsx + sx], 1);
+                    ++nloc;
+                }
+        __syncthreads();
+        if (threadIdx.x < nsr) {
+            const int c = s_cnt[threadIdx.x];
+            s_base[threadIdx.x] = c ? atomicAdd(&bin_cnt[b * nsr + threadIdx.x], c) : 0;
+        }
+        __syncthreads();
+        if (mask) {
+            int q = 0;
+            for (int sy = sy0; sy <= sy1; ++sy)
+                for (int sx = sx0; sx <= sx1; ++sx, ++q) {
+                    const int sr = sy * nsx + sx;
+                    const int at = q < 4 ? s_base[sr] + local[q] : atomicAdd(&bin_cnt[b * nsr + sr], 1);
+                    bin_list[((long)b * nsr + sr) * F + at] = fi;
+                }
+        }
     }
     HM_STAMP_END(0);
 }

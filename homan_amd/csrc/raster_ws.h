@@ -30,6 +30,11 @@ static inline size_t sweep_slot_cap(int B, int F) { return sweep_ucap(B, F) + (s
 
 // workspace layout helper (bytes), all chunks 256-byte aligned
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// face bins of a render of S^2 pixels (raster_common.h): the bins a frame of that size really has - 0 without bins -, their
+// counters (+ one ticket word per super-region; a region bin has none) and their lists of F entries, the safe worst case
+static inline size_t ws_bins(int S) { return (size_t)hm_bins_per_frame(2 * S); }
+static inline size_t ws_bin_counter_bytes(int B, int S) { return (size_t)B * ws_bins(S) * (hm_region_bins(2 * S) ? 4 : 8); }
+static inline size_t ws_bin_list_bytes(int B, int F, int S) { return (size_t)B * ws_bins(S) * F * 4; }
 
 struct SilWs {
     unsigned int* counter; float* frame_rec;
@@ -59,9 +64,10 @@ static inline SilWs carve(void* ws, int B, int V, int F, int S)
     w.planes = (unsigned short*)p; p += al256((size_t)B * is * (is / 16) * 4) * 2;      // (B, T, T, 4, 16) u16
     w.parts = (double*)p; p += al256((size_t)B * F * 24 * 4);      // (6 doubles per face for the sweeps; 9 floats for the depth backward)
     w.owned = (unsigned char*)p; p += al256((size_t)B * F * 2);
-    w.bin_cnt = (int*)p; w.bin_done = (unsigned int*)(p + (size_t)B * SR_MAX * 4); p += al256((size_t)B * SR_MAX * 8);
+    w.bin_cnt = (int*)p; w.bin_done = hm_region_bins(2 * S) ? nullptr : (unsigned int*)(p + (size_t)B * ws_bins(S) * 4);
+    p += al256(ws_bin_counter_bytes(B, S));
     w.region_state = (unsigned char*)p; p += al256((size_t)B * (S / 16) * (S / 16));
-    w.bin_list = (int*)p; p += al256((size_t)B * SR_MAX * F * 4);
+    w.bin_list = (int*)p; p += al256(ws_bin_list_bytes(B, F, S));
     w.lrec = (uint4*)p; p += al256(4 * (size_t)B * is * (is / 64) * 16);
     w.lsum = (unsigned short*)p; p += al256((size_t)B * 2 * is * 16);
     w.srcs = (SweepSrc*)p; p += al256(4 * (size_t)B * is * is * sizeof(SweepSrc));
@@ -96,7 +102,7 @@ static inline bool hm_offsets_fit_32(int B, int S)
 }
 
 // ---------------------------------------------------------------- launchers (one per kernel family, defined next to the kernels)
-// raster_setup.hip: k_setup_faces, grid (nfb + vertex blocks, B).  bins == NULL: no super-region bins (is > 1024)
+// raster_setup.hip: k_setup_faces, grid (nfb + vertex blocks, B).  bins == NULL: no face bins (is > 1024)
 HM_INTERNAL void hm_launch_setup_faces(const SilWs& w, const float* verts, const float* K, float orig_size, const int* faces,
                                        int faces_bstride, int B, int V, int F, int is, int* bins, const float* rigid_rot6d,
                                        const float* rigid_trans, const float* rigid_scale, int rigid_abs, int clip_len,

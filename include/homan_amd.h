@@ -274,6 +274,8 @@ int hm_sil_invalidate_outputs(void* workspace, int B, int V, int F, int S, hipSt
 int hm_sil_read_parts(const void* workspace, int B, int V, int F, int S, double* out, hipStream_t stream);
 /* per-face screen boxes (B,F) x 8 bytes {x0|winding<<14, y0, x1, y1} u16 */
 int hm_sil_read_boxes(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream);
+/* "owns at least one sample" flags of the last forward, (B,2,F) bytes: [b][0][f] face f as stored, [b][1][f] its reversed copy */
+int hm_sil_read_owned(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream);
 
 /* ------------------------------------------------------------------ soft silhouettes (NON-PARITY extra; csrc/softsil.hip)
  * Liu, Li, Chen, Li, "Soft Rasterizer: A Differentiable Renderer for Image-based 3D Reasoning", ICCV 2019, silhouette branch:

@@ -229,7 +229,7 @@ the object's depth render).
 |---|---|---|---|
 | `faces9` (packed face buffer) | (B,F,3,3) f32 NDC | 3.2 MB | `k_setup_faces` → `k_raster_fwd` (record build), sweep work list |
 | `boxes` | (B,F) 4×u16 sample box + 2-bit winding mask | 0.7 MB | `k_setup_faces` → `k_raster_fwd`, sweep work list |
-| `bin_cnt`, `bin_list` | (B,64) i32 ; (B,64,F) i32 — faces per 64² super-region (128² above 512² samples) | ≤ 23 MB (≈ 0.6 MB used) | `k_setup_faces` → `k_raster_fwd` |
+| `bin_cnt`, `bin_list` | (B,n²) i32 ; (B,n²,F) i32, n² = the bins a render of that size really has: one per 32² region up to 512² samples (n = S/16 ≤ 16; entry = face \| winding mask ≪ 30), one per 128² super-region above (n ≤ 8, + one ticket word per bin), none above 1024² | 30 KB ; ≤ 92 MB of address space (≈ 0.6 MB used) | `k_setup_faces` → `k_raster_fwd` |
 | `idx_map` | (B,512,512) i32, −1 = background | 31.5 MB | `k_raster_fwd` → `k_bwd_lines`, `k_bwd_sweep`, `k_depth_bwd_faces` |
 | `alpha16` | (B,32,32,16) u16, 1 bit / sample, tile-blocked | 1 MB | `k_raster_fwd` → `k_bwd_masks` (generic backward only) |
 | `pooled`, `dimg` (`gimg`: generic backward) | (B,256,256) f32 | 7.9 MB each | raster → reduce / lines |
@@ -266,8 +266,8 @@ workgroups in the order of a single-clip launch - which is why a batched step is
 
 | Kernel | Work decomposition | Bound | Alg. bytes / launch |
 |---|---|---|---|
-| `k_setup_faces` | thread / face: optional rigid transform of the mesh-space vertex (the silhouette chain does not wait for `hm_rigid_fwd`), projects its 3 vertices (no separate projection launch), windings, tight sample box; bins the face into 64² super-regions (128² above 512² samples; LDS-aggregated counts, one global atomic per (workgroup, bin)); extra workgroups write the camera-space vertices for the other losses (same arithmetic as `k_rigid_fwd`: the hand-side stream no longer opens with a transform launch) | HBM | B·(V·24 + F·(12+36+8+2+5)) = 6.7 MB |
-| **`k_raster_fwd`** | workgroup = one 32×32-sample region: scans the faces of its super-region; candidates are split by WINDING CLASS - the class that holds the camera-facing surface of the mesh (a scheduling hint set by `calibrate()` from the index map; any value is correct) fills the candidate array from the front, the other from the back; one thread per candidate builds the face record in LDS (+ the nearest depth the face can produce) - BOTH classes in one pass, wave 0 up to 64 near-class records while wave 1 builds up to 64 far-class records (one round trip to the packed faces and one stretch of record arithmetic per round instead of one per class: the far class's pass had been a quarter of an active workgroup's time with three waves at its barrier; per-class prefix sums are per-wave scans); the (candidate, 4×4-sample block) units are **flattened** over the 256 threads (binary search of the exclusive unit counts); visibility = `ds_min_u64` on an LDS z-buffer keyed (depth bits ≪ 32 \| face) = strict z test in ascending face order, bit-exact.  The near class runs first; then per 4×4 block the largest owner depth is taken (`hz`), and the units of the far class are first tested against it, 64 per wave trip, the survivors queued per wave and the unit body run on FULL waves of survivors (a divergent early-out would leave the wave paying for its one visible unit: on a closed mesh ~85 % of the far units are hidden).  Sample positions of power-of-two grids by one multiplication (eight IEEE divisions per unit before).  Epilogue per 8×8 output tile: index map, pooled silhouette, fused masked-MSE terms, alpha plane and the four sweep bit planes of the backward (one full cache line per tile, ballots picked with selects: no scratch); in a fixed loop (`persistent_outputs`) an empty bin in front of outputs that already hold the empty pattern leaves before touching LDS (60 % of the workgroups).  The inside test of a unit is arithmetic, not compares: `rv < cv` is the SIGN BIT of `rv - cv` (after `rv + 0.0f`, which turns the one case where the sign lies, -0, into +0), the three edges' differences OR-ed into sixteen accumulators and shifted into the mask by one `v_alignbit` per sample - 156 instead of 221 instructions per unit (round 5); faces with a vertex projected beyond 1e15 are culled by the face setup and by the oracle (their edge functions overflow to inf - inf).  Wave-uniform values (work-order entry, wave index and everything derived) go through `readfirstlane` into scalar registers.  25 KB of LDS and 80 VGPRs (no spills): 6 workgroups per CU (7 per CU at 72 registers: measured slower, EXPERIMENTS r5) | latency × residency (5-6 dependent round trips per active workgroup), VALU-bound only when the GPU is full (clip batch, pose initialisation) | B·(F·49 + 512²·4 + 4·S²·4 + 5·512²/8) = **72.2 MB** |
+| `k_setup_faces` | thread / face: optional rigid transform of the mesh-space vertex (the silhouette chain does not wait for `hm_rigid_fwd`), projects its 3 vertices (no separate projection launch), windings, tight sample box; bins the face: up to 512² samples into every 32²-sample REGION its box touches (the raster workgroup's own box and its own overlap test, done once here instead of in four workgroups; entry = face \| winding mask ≪ 30; counts per bin in LDS, one global reservation per (workgroup, bin), entries placed by counting the reserved base up in LDS - two `int[256]`, a quad across the image goes into all 256 bins without a global atomic of its own), above that into 128² super-regions (one LDS slot for the first four bins of a face, one global atomic per further bin).  Workspace: counters and lists are sized by the bins a render of its S has, lists F entries per bin (the safe worst case) - cfg2 (B = 30, 256 bins): 30 KB + 92 MB of address space (23 MB with 64² super-regions); the 8-clip batch (B = 240): 240 KB + 737 MB; `--pose-init 500` (500 renders of 256² samples = 64 bins, as many as before): 125 KB + 384 MB, unchanged; extra workgroups write the camera-space vertices for the other losses (same arithmetic as `k_rigid_fwd`: the hand-side stream no longer opens with a transform launch) | HBM | B·(V·24 + F·(12+36+8+2+5)) = 6.7 MB |
+| **`k_raster_fwd`** | workgroup = one 32×32-sample region: up to 512² samples it reads the list of ITS OWN bin - every entry is a candidate and carries its winding mask, so the scan loads no box and tests none; it empties the bin's count itself (one reader, no ticket; the store sits behind the scan's first barrier, since every wave loads the count for itself) and a region no face touches leaves at the top - above 512² samples it scans the faces of its super-region against their boxes and the last of the 16 readers empties the count through a ticket word; candidates are split by WINDING CLASS - the class that holds the camera-facing surface of the mesh (a scheduling hint set by `calibrate()` from the index map; any value is correct) fills the candidate array from the front, the other from the back; one thread per candidate builds the face record in LDS (+ the nearest depth the face can produce) - BOTH classes in one pass, wave 0 up to 64 near-class records while wave 1 builds up to 64 far-class records (one round trip to the packed faces and one stretch of record arithmetic per round instead of one per class: the far class's pass had been a quarter of an active workgroup's time with three waves at its barrier; per-class prefix sums are per-wave scans); the (candidate, 4×4-sample block) units are **flattened** over the 256 threads (binary search of the exclusive unit counts); visibility = `ds_min_u64` on an LDS z-buffer keyed (depth bits ≪ 32 \| face) = strict z test in ascending face order, bit-exact.  The near class runs first; then per 4×4 block the largest owner depth is taken (`hz`), and the units of the far class are first tested against it, 64 per wave trip, the survivors queued per wave and the unit body run on FULL waves of survivors (a divergent early-out would leave the wave paying for its one visible unit: on a closed mesh ~85 % of the far units are hidden).  Sample positions of power-of-two grids by one multiplication (eight IEEE divisions per unit before).  Epilogue per 8×8 output tile: index map, pooled silhouette, fused masked-MSE terms, alpha plane and the four sweep bit planes of the backward (one full cache line per tile, ballots picked with selects: no scratch); in a fixed loop (`persistent_outputs`) an empty bin in front of outputs that already hold the empty pattern leaves before touching LDS (60 % of the workgroups).  The inside test of a unit is arithmetic, not compares: `rv < cv` is the SIGN BIT of `rv - cv` (after `rv + 0.0f`, which turns the one case where the sign lies, -0, into +0), the three edges' differences OR-ed into sixteen accumulators and shifted into the mask by one `v_alignbit` per sample - 156 instead of 221 instructions per unit (round 5); faces with a vertex projected beyond 1e15 are culled by the face setup and by the oracle (their edge functions overflow to inf - inf).  Wave-uniform values (work-order entry, wave index and everything derived) go through `readfirstlane` into scalar registers.  25 KB of LDS and 80 VGPRs (no spills): 6 workgroups per CU (7 per CU at 72 registers: measured slower, EXPERIMENTS r5) | latency × residency (5-6 dependent round trips per active workgroup), VALU-bound only when the GPU is full (clip batch, pose initialisation) | B·(F·49 + 512²·4 + 4·S²·4 + 5·512²/8) = **72.2 MB** |
 | `k_setup_faces_multi`, `k_raster_fwd_multi` (`hm_sil_fwd_multi`, round 6) | the two kernels' BODIES (`setup_faces_body`, `raster_fwd_body`: `__forceinline__` functions over the kernels' argument lists) called with one of up to four per-render argument blocks held in the kernarg segment; a workgroup finds its render by a scalar search over the renders' first workgroups (raster) / first frames (setup: grid = largest block count x all frames, surplus blocks leave at once) - every argument stays a scalar load, same registers (80 / 38), no scratch; renders differ in mesh (V, F, vertex and face arrays), cameras, masks, outputs, render size and workspace, each backward runs on its own workspace as before.  Used by the fused loop for the ordinal depth term (silhouette render + the object's depth render: 41 + 7 + 34 µs of launches become 56); it is also the raster-stage entry point for frames of DIFFERENT meshes (one render per mesh) | as the bodies | per render as above |
 | `k_sil_reduce` | block / frame + last-block finish.  One clip: the same body rides as B extra workgroups at the front of the `k_bwd_lines` launch (`hm_sil_bwd_clips(..., loss_out)`): the value is only logged, so it costs no launch; a clip batch keeps it on the third stream | latency | 0.5 MB |
 | `k_bwd_masks` | generic backward only (arbitrary `dL/dsilhouette`, or a negative loss weight): wave / tile, sweep planes via ballots | HBM | ≈ 21 MB |
@@ -383,8 +383,8 @@ cfg2 clip, every kernel at its latency floor):
 
 | kernel | b1 (1 frame) | cfg1 (10 × 128²) | cfg2 (30 × 256²) | dependent global round trips of its critical workgroup |
 |---|---|---|---|---|
-| `k_setup_faces` | 6.5 | 6.3 | 9.2 | kernargs, faces → vertices, bin count (returning atomic), list store |
-| `k_raster_fwd` | 18.2 | 17.3 | 49.6 (40 in-graph) | kernargs, launch-order entry, bin count + state, list, boxes, faces, ticket, keep / ref |
+| `k_setup_faces` | 6.5 | 6.3 | 9.2 (8.2 with region bins) | kernargs, faces → vertices, bin count (returning atomic), list store |
+| `k_raster_fwd` | 18.2 | 17.3 | 49.6 (40 in-graph; region bins: 43.2 → 40.1 under the profiler, same box) | kernargs, launch-order entry, bin count + state, list, faces (+ boxes, same trip), keep / ref - the box hop of the scan and the bin ticket went with the region bins (EXPERIMENTS.md) |
 | `k_bwd_lines` | 9.7 | 10.9 | 21.1 | kernargs, plane words, gradient + owner gathers per word (work-list blocks: scan + one atomic) |
 | `k_bwd_sweep` | 17.5 | 18.8 | 46.1 | totals, unit table, face records, summaries + owner + alpha, line records, sources |
 | `k_rigid_bwd_x` | 15.5 | 9.0 | 17.3 | offsets → items → corner sums, chunk records + ticket, records |

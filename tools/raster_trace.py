@@ -1,7 +1,8 @@
 """Where does an active k_raster_fwd workgroup spend its time?  Debug build with per-workgroup phase stamps (no atomics):
     tools/ab_build.sh trace -DRASTER_TRACE ; HOMAN_AMD_LIB=variants/lib_trace.so python tools/raster_trace.py [--frames 30] [--depth]
 Prints, for the raster launch of iteration `--warm` of a cfg2-shaped fit (replayed from the captured graph, next to the hand-side
-kernels as in the real loop), the phase durations of wave 0 in microseconds - all active workgroups, and the slowest tenth."""
+kernels as in the real loop), the phase durations of wave 0 in microseconds - all active workgroups (those with a candidate), and
+the slowest tenth - and the number of workgroups that scanned a list for nothing."""
 import argparse
 import copy
 import ctypes
@@ -49,7 +50,9 @@ def main():
     t = np.frombuffer(buf, dtype=np.uint32).reshape(nwg, 9).astype(np.float64)
     ph = t[:, :6] * 0.01                        # 10 ns ticks -> us
     tot = ph.sum(1)
-    act = tot > 0
+    cand = t[:, 7] > 0
+    scan_only = (tot > 0) & ~cand                # walked a list and kept no candidate (super-region bins; a region bin lists candidates only)
+    act = (tot > 0) & cand
     start = t[:, 6]
     names = ["scan", "records", "near_units", "wait+hz", "far_units", "epilogue"]
     print(f"frames {a.frames} {a.depth or ''}: workgroups {nwg}, active {int(act.sum())}; launch span (first start .. last end of active) "
@@ -60,6 +63,8 @@ def main():
               f"{np.percentile(tot[sel], 90):.2f} max {tot[sel].max():.2f} us; candidates near {np.mean(t[sel, 7] % 65536):.0f} far "
               f"{np.mean(t[sel, 7] // 65536):.0f}; units near {np.mean(t[sel, 8] % 65536):.0f} far {np.mean(t[sel, 8] // 65536):.0f}")
         print("     " + "  ".join(f"{n} {p[:, k].mean():.2f}" for k, n in enumerate(names)))
+    print(f"  workgroups that scanned and kept no candidate: {int(scan_only.sum())}, of them {int((scan_only & (ph[:, 5] == 0)).sum())} left "
+          f"before the epilogue" + (f"; their scan: mean {ph[scan_only, 0].mean():.2f} max {ph[scan_only, 0].max():.2f} us" if scan_only.any() else ""))
     show(act, "active")
     thr = np.percentile(tot[act], 90)
     show(act & (tot >= thr), "slowest tenth")
