@@ -19,109 +19,13 @@
 // the batch.  No floating-point atomics.
 #include "hm_common.h"
 #include "inside_test.h"     // orient2, ray_x_crosses
+#include "surfdist_walk.h"   // SdFace, sd_load_face, sd_closest: the per-face walk, shared with csrc/surfcontact.hip
 
 #define SD_THREADS 256
 #define SD_CHUNK 256                     // faces staged per pass: one record per thread (ops.SURFDIST_CHUNK mirrors it)
 #define SD_MAX_GRID_Z 65535
 #define SD_TARGET_BLOCKS 1024            // four workgroups on each of the 256 CUs before the faces stop being split
 #define SD_EMPTY 0x7f800000ffffffffull   // (bits(+inf) << 32) | (unsigned)-1: no face yet
-
-#define SD_SKIPPED 0
-#define SD_TRIANGLE 1
-#define SD_SEGMENTS 2
-
-struct SdFace { float a[3], b[3], c[3], ab[3], ac[3]; int kind; };      // 16 words: four b128 LDS reads
-
-__device__ __forceinline__ float sd_dot(const float* u, const float* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-__device__ __forceinline__ bool sd_finite(float x) { return fabsf(x) <= 3.4028234e38f; }       // (a NaN fails)
-
-// face f of the frame's mesh as a record; SD_SKIPPED when it names a vertex outside [0, V) or holds a non-finite coordinate
-__device__ __forceinline__ void sd_load_face(const float* __restrict__ v, const int* __restrict__ faces, long f, int V,
-                                             SdFace& r)
-{
-    const int* t = faces + 3 * f;
-    const int i0 = t[0], i1 = t[1], i2 = t[2];
-    r.kind = SD_SKIPPED;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r.a[k] = r.b[k] = r.c[k] = r.ab[k] = r.ac[k] = 0.f;
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) return;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        r.a[k] = v[3L * i0 + k]; r.b[k] = v[3L * i1 + k]; r.c[k] = v[3L * i2 + k];
-        ok = ok && sd_finite(r.a[k]) && sd_finite(r.b[k]) && sd_finite(r.c[k]);
-        r.ab[k] = r.b[k] - r.a[k];
-        r.ac[k] = r.c[k] - r.a[k];
-    }
-    if (!ok) return;
-    const float nx = r.ab[1] * r.ac[2] - r.ab[2] * r.ac[1];
-    const float ny = r.ab[2] * r.ac[0] - r.ab[0] * r.ac[2];
-    const float nz = r.ab[0] * r.ac[1] - r.ab[1] * r.ac[0];
-    r.kind = (nx == 0.f && ny == 0.f && nz == 0.f) ? SD_SEGMENTS : SD_TRIANGLE;
-}
-
-// clamped projection of p on the segment u -> v: q, and |p - q|^2
-__device__ __forceinline__ float sd_segment(const float* p, const float* u, const float* v, float* q)
-{
-    const float e[3] = {v[0] - u[0], v[1] - u[1], v[2] - u[2]};
-    const float w[3] = {p[0] - u[0], p[1] - u[1], p[2] - u[2]};
-    const float len2 = sd_dot(e, e);
-    float t = 0.f;
-    if (len2 > 0.f) {
-        t = sd_dot(w, e) / len2;
-        t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-    }
-    float d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { q[k] = u[k] + t * e[k]; d[k] = p[k] - q[k]; }
-    return sd_dot(d, d);
-}
-
-// closest point q of the face to p and D = |p - q|^2 (kind != SD_SKIPPED)
-__device__ __forceinline__ float sd_closest(const float* p, const SdFace& r, float* q)
-{
-    if (r.kind == SD_SEGMENTS) {                                  // ab, bc, ca; ties to the first
-        float D = sd_segment(p, r.a, r.b, q), q2[3];
-        float D2 = sd_segment(p, r.b, r.c, q2);
-        if (D2 < D) { D = D2; q[0] = q2[0]; q[1] = q2[1]; q[2] = q2[2]; }
-        D2 = sd_segment(p, r.c, r.a, q2);
-        if (D2 < D) { D = D2; q[0] = q2[0]; q[1] = q2[1]; q[2] = q2[2]; }
-        return D;
-    }
-    const float ap[3] = {p[0] - r.a[0], p[1] - r.a[1], p[2] - r.a[2]};
-    const float bp[3] = {p[0] - r.b[0], p[1] - r.b[1], p[2] - r.b[2]};
-    const float cp[3] = {p[0] - r.c[0], p[1] - r.c[1], p[2] - r.c[2]};
-    const float d1 = sd_dot(r.ab, ap), d2 = sd_dot(r.ac, ap), d3 = sd_dot(r.ab, bp), d4 = sd_dot(r.ac, bp);
-    const float d5 = sd_dot(r.ab, cp), d6 = sd_dot(r.ac, cp);
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    const float e1 = d4 - d3, e2 = d5 - d6;
-    if (d1 <= 0.f && d2 <= 0.f) {                                  // A
-        q[0] = r.a[0]; q[1] = r.a[1]; q[2] = r.a[2];
-    } else if (d3 >= 0.f && d4 <= d3) {                            // B
-        q[0] = r.b[0]; q[1] = r.b[1]; q[2] = r.b[2];
-    } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {              // AB
-        const float t = d1 / (d1 - d3);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = r.a[k] + t * r.ab[k];
-    } else if (d6 >= 0.f && d5 <= d6) {                            // C
-        q[0] = r.c[0]; q[1] = r.c[1]; q[2] = r.c[2];
-    } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {              // AC
-        const float t = d2 / (d2 - d6);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = r.a[k] + t * r.ac[k];
-    } else if (va <= 0.f && e1 >= 0.f && e2 >= 0.f) {              // BC
-        const float t = e1 / (e1 + e2);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = r.b[k] + t * (r.c[k] - r.b[k]);
-    } else {                                                       // interior
-        const float s = (va + vb) + vc;
-        const float tv = vb / s, tw = vc / s;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = (r.a[k] + tv * r.ab[k]) + tw * r.ac[k];
-    }
-    const float d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-    return sd_dot(d, d);
-}
 
 // the outputs of point `at` (= b * N + i) from its merged values; face < 0: no face counted
 __device__ __forceinline__ void sd_write(const float* __restrict__ points, const float* __restrict__ vb,

@@ -82,6 +82,10 @@ class FusedStepper:
     def __init__(self, model, loss_weights, lr, max_steps, capture=True, shared_scale=False, group=None, collectives=True):
         from . import constants, ops
         from .clipbatch import ClipBatch, ClipReduceWorkspace
+        if float(loss_weights.get("lw_surf_attr", 0)) > 0 or float(loss_weights.get("lw_surf_rep", 0)) > 0:
+            # (checked before anything is built: mode="auto" and ClipFitter fall back as they do for sil_mode="soft")
+            raise NotImplementedError("lw_surf_attr / lw_surf_rep: the surface contact loss is not in the fused launch sequence "
+                                      "(mode='graph' or 'eager')")
         for one in (model.models if isinstance(model, ClipBatch) else model if isinstance(model, (list, tuple)) else [model]):
             if len(one.hand_sides) not in (1, 2):
                 raise NotImplementedError("one or two hands per frame")

@@ -59,8 +59,14 @@ class HOMan(nn.Module):
                  optimize_mano_beta=True, inter_type="centroid", image_size=640,
                  # homan_amd extensions (keyword-only use)
                  mano_model=None, mano_root="extra_data/mano", rend_size=constants.REND_SIZE, sync_metrics=True,
-                 ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4):
+                 ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4, surface_contact_thresh=constants.CONTACT_THRESH,
+                 surface_collision_thresh=constants.COLLISION_THRESH, surface_two_way=False, surface_contact_zones="all"):
         # (host-side checks of the options first: no device is touched before they pass)
+        if surface_contact_zones not in ("all", "tips"):
+            raise ValueError(f"surface_contact_zones {surface_contact_zones} not in [all|tips]")
+        for name, c in (("surface_contact_thresh", surface_contact_thresh), ("surface_collision_thresh", surface_collision_thresh)):
+            if not 0 < float(c) < float("inf"):
+                raise ValueError(f"{name} {c} must be a positive number (metres)")
         if sil_mode not in ("nmr", "soft"):
             raise ValueError(f"sil_mode {sil_mode} not in [nmr|soft]")
         if not float(sil_sigma) > 0 or float(sil_sigma) == float("inf"):
@@ -189,6 +195,11 @@ class HOMan(nn.Module):
                                   ops.CollisionContext(rev, self.faces_object[0], batch, 778, num_verts_object, dev),
                                   ops.CollisionContext(rev, self.faces_object[0], batch, 778, num_verts_object, dev))
         self._mano_cache = None
+        # surface contact loss (a homan_amd extra): on when forward() is given lw_surf_attr / lw_surf_rep;
+        # its contexts are built at the first forward that needs them (before any capture: GraphStepper's warm-up forwards)
+        self.surface_contact_thresh, self.surface_collision_thresh = float(surface_contact_thresh), float(surface_collision_thresh)
+        self.surface_two_way, self.surface_contact_zones = bool(surface_two_way), surface_contact_zones
+        self._surf_ctxs = None
         # ordinal depth term: the reference's own call site cannot run (see forward()); `ordinal_depth=True` opts into the
         # loss the method describes (homan.py:384-419 + lossutils.py:133-169) instead of reproducing that TypeError
         self.ordinal_depth = bool(ordinal_depth)
@@ -487,8 +498,20 @@ class HOMan(nn.Module):
         sil_h, dep_h = ops.depth_render(verts_hand, self.camintr, ctx_h, 1.0)
         return {"loss_depth": ops.ordinal_depth_loss(dep_o, dep_h, sil_o, sil_h, m_o, m_h, self.reduce_ws)}
 
+    def compute_surface_contact_loss(self, verts_hand, verts_object):
+        """({"loss_surf_attr", "loss_surf_rep"}, {"surf_inside_share"}) on the model's options (lossutils)"""
+        if self._surf_ctxs is None:
+            self._surf_ctxs = lossutils.surface_contact_contexts(
+                verts_object.shape[0], self.hand_nb, np.asarray(self.mano_model.closed_faces), self.faces_object[0],
+                verts_object.shape[1], verts_object.device, self.surface_two_way, self.surface_contact_zones)
+        return lossutils.compute_surface_contact_loss(verts_hand, verts_object, self._surf_ctxs, self.surface_contact_thresh,
+                                                      self.surface_collision_thresh)
+
     def forward(self, loss_weights=None):
-        """reference homan.py:421-508: a loss whose weight is zero is not computed."""
+        """reference homan.py:421-508: a loss whose weight is zero is not computed.  The one exception to "None computes
+        everything" is the surface contact loss, an extra: it runs only when loss_weights holds a positive lw_surf_attr or
+        lw_surf_rep (the term with a positive weight is returned), so forward(None) and weight sets without those keys
+        return the reference's keys."""
         lw = loss_weights
         on = lambda key: lw is None or lw[key] > 0
         loss_dict, metric_dict = {}, {}
@@ -519,6 +542,10 @@ class HOMan(nn.Module):
         if on("lw_contact"):
             l_contact, nn_cache = lossutils.compute_contact_loss(verts_hand_det_scale, verts_object, self.reduce_ws)
             loss_dict.update(l_contact)
+        if lw is not None and (lw.get("lw_surf_attr", 0) > 0 or lw.get("lw_surf_rep", 0) > 0):
+            l, m = self.compute_surface_contact_loss(verts_hand_det_scale, verts_object)
+            loss_dict.update({k: v for k, v in l.items() if lw.get(k.replace("loss", "lw"), 0) > 0})
+            metric_dict.update({k: v.item() if self.sync_metrics else v.detach() for k, v in m.items()})
         if on("lw_v2d_hand"):
             l, m = self.losses.compute_verts2d_loss_hand(verts_hand, image_size=self.image_size,
                                                          min_hand_size=70 if self.optimize_object_scale else 1000)

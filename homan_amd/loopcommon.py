@@ -122,13 +122,16 @@ def _weighted_total(loss_dict, loss_weights):
 def build_model(person_parameters, object_parameters, class_name="default", objvertices=None, objfaces=None,
                 camintr=None, hand_proj_mode="persp", optimize_mano=False, optimize_mano_beta=True,
                 optimize_object_scale=False, state_dict=None, image_size=640, mano_model=None, rend_size=256,
-                sync_metrics=True, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4):
+                sync_metrics=True, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4,
+                surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all"):
     kw = collate_inputs(person_parameters, object_parameters, objvertices, objfaces)
     model = HOMan(camintr=camintr, class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode,
                   optimize_mano=optimize_mano, optimize_mano_beta=optimize_mano_beta,
                   optimize_object_scale=optimize_object_scale, image_size=image_size, mano_model=mano_model,
                   rend_size=rend_size, sync_metrics=sync_metrics, ordinal_depth=ordinal_depth, sil_mode=sil_mode,
-                  sil_sigma=sil_sigma, **kw)
+                  sil_sigma=sil_sigma,
+                  surface_contact_thresh=surface_contact_thresh, surface_collision_thresh=surface_collision_thresh,
+                  surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones, **kw)
     if state_dict is not None:
         model.load_state_dict(state_dict, strict=False)
     return model

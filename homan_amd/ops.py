@@ -1204,3 +1204,153 @@ def point_mesh_distance(points, verts, faces, closest=False):
                                                      _lib.ptr(out.get("closest")), _lib.ptr(ws), _lib.stream()),
                    "hm_point_mesh_distance")
     return out
+
+
+# =============================================================================== surface contact loss
+def surface_contact_log2q(N, weight_max=1.0, contact_thresh=0.010, collision_thresh=0.020):
+    """The grid 2^L of the exact sums of hm_surface_contact_fwd (include/homan_amd.h): L = ceil(log2(N M)) - 50 with
+    M = max(weight_max, 1) * max(contact_thresh, collision_thresh, 1), which bounds every addend: N addends of one frame - all
+    the points on one face is a legal input - stay below 2^51 quanta.  N = 778 at unit weights gives -40."""
+    import math
+    M = max(float(weight_max), 1.0) * max(float(contact_thresh), float(collision_thresh), 1.0)
+    if not (N >= 1 and math.isfinite(M)):
+        raise ValueError(f"surface_contact_log2q: N {N}, bound {M}")
+    return math.ceil(math.log2(N * M)) - 50
+
+
+def _check_surface_thresholds(contact_thresh, collision_thresh):
+    for name, c in (("contact_thresh", contact_thresh), ("collision_thresh", collision_thresh)):
+        with np.errstate(over="ignore"):
+            c32 = np.float32(c)
+        if not (np.isfinite(c32) and c32 > 0):
+            raise ValueError(f"{name} must be positive and finite in fp32, got {c}")
+    return float(contact_thresh), float(collision_thresh)
+
+
+class SurfaceContactContext:
+    """Workspace and static unit-gradient buffers of `surface_contact_loss` for points (B,N,3) against meshes (B,V,3) of the
+    topology faces (F,3) (host array or tensor of integers in [0, V)).  A context serves one forward at a time: the backward
+    of a forward reads the context's buffers, so it has to run before the context's next forward (one context per call site)."""
+
+    def __init__(self, B, N, V, faces, device):
+        B, N, V = int(B), int(N), int(V)
+        if B < 1 or N < 1 or V < 1:
+            raise ValueError(f"SurfaceContactContext: B, N, V must be positive, got {(B, N, V)}")
+        faces = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.dtype.kind not in "iu":
+            raise ValueError(f"faces: expected a non-empty integer (F, 3) array, got {faces.dtype} {faces.shape}")
+        if not torch.cuda.is_available():
+            raise _lib.HomanAmdError("homan_amd.ops.SurfaceContactContext needs the GPU (there is no CPU fallback)")
+        dev = torch.device(device)
+        self.B, self.N, self.V, self.F, self.device = B, N, V, int(faces.shape[0]), dev
+        self.faces = torch.from_numpy(np.array(faces, dtype=np.int32)).to(dev)             # (a writable, contiguous copy)
+        self.ws = torch.zeros(_lib.lib().hm_surface_contact_workspace_bytes(B, N, V, self.F), dtype=torch.uint8, device=dev)
+        self.grad_points = torch.zeros(B, N, 3, device=dev)
+        self.inside = torch.zeros(B, N, dtype=torch.int32, device=dev)
+        self.grad_verts_attr = torch.zeros(B, V, 3, device=dev)
+        self.grad_verts_rep = torch.zeros(B, V, 3, device=dev)
+        self._weights = (None, None, 1.0)              # (key of the caller's tensor, fp32 device copy, its maximum)
+        self.calls = 0                                 # forwards run on these buffers
+
+    def weights(self, weights, weight_max=None):
+        """the caller's per-point weights as (fp32 device tensor or None, maximum).  The maximum is read on the host once per
+        tensor (and version of it); pass `weight_max` to skip that read - it synchronises, which a stream capture forbids."""
+        if weights is None:
+            return None, 1.0
+        if not isinstance(weights, torch.Tensor) or not weights.is_floating_point() or tuple(weights.shape) != (self.N,):
+            raise ValueError(f"weights: expected a float tensor of shape ({self.N},), got "
+                             f"{getattr(weights, 'dtype', type(weights))} {tuple(getattr(weights, 'shape', ()))}")
+        key = (weights.data_ptr(), weights._version, weights.device, weight_max)
+        if self._weights[0] != key:
+            w = weights.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if weight_max is None:
+                lo, hi = float(w.min()), float(w.max())
+                if not (lo >= 0 and np.isfinite(hi)):
+                    raise ValueError(f"weights must be finite and >= 0, got [{lo}, {hi}]")
+                weight_max = hi
+            self._weights = (key, w, float(weight_max))
+        return self._weights[1], self._weights[2]
+
+
+def _check_surface_inputs(points, verts, sctx):
+    if not isinstance(sctx, SurfaceContactContext):
+        raise ValueError(f"ctx: expected a SurfaceContactContext, got {type(sctx)}")
+    for name, t, n in (("points", points, sctx.N), ("verts", verts, sctx.V)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError(f"{name}: expected a float tensor, got {getattr(t, 'dtype', type(t))}")
+        if tuple(t.shape) != (sctx.B, n, 3):
+            raise ValueError(f"{name}: expected {(sctx.B, n, 3)} (the context's sizes), got {tuple(t.shape)}")
+
+
+def _surface_contact_run(points, verts, sctx, wdev, c_a, c_r, log2q, detail=None):
+    """one hm_surface_contact_fwd on the context's buffers -> out (2,) = (A, R), a new tensor"""
+    out = torch.empty(2, device=sctx.device)
+    d = detail or {}
+    _lib.check(_lib.lib().hm_surface_contact_fwd(_lib.ptr(points), _lib.ptr(verts), _lib.ptr(sctx.faces), _lib.ptr(wdev), sctx.B,
+                                                 sctx.N, sctx.V, sctx.F, c_a, c_r, log2q, _lib.ptr(out),
+                                                 _lib.ptr(sctx.grad_points), _lib.ptr(sctx.inside),
+                                                 _lib.ptr(sctx.grad_verts_attr), _lib.ptr(sctx.grad_verts_rep),
+                                                 _lib.ptr(d.get("value")), _lib.ptr(d.get("bary")), _lib.ptr(d.get("d2")),
+                                                 _lib.ptr(d.get("face")), _lib.ptr(sctx.ws), _lib.stream()),
+               "hm_surface_contact_fwd")
+    sctx.calls += 1                    # (whose unit gradients the buffers hold: the backward checks it)
+    return out
+
+
+class _SurfaceContactLoss(torch.autograd.Function):
+    """hm_surface_contact_fwd / _bwd (csrc/surfcontact.hip): the forward leaves the unit gradients in the context, the backward
+    scales them by the two upstreams."""
+
+    @staticmethod
+    def forward(ctx, points, verts, sctx, wdev, c_a, c_r, log2q):
+        out = _surface_contact_run(_f32(points.detach()), _f32(verts.detach()), sctx, wdev, c_a, c_r, log2q)
+        ctx.sctx, ctx.call = sctx, sctx.calls
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_attr, g_rep):
+        s = ctx.sctx
+        if ctx.call != s.calls:
+            raise RuntimeError("surface_contact_loss: the context has run another forward since this one; its unit gradients are "
+                               "gone (one SurfaceContactContext per call site, backward before the next forward)")
+        want_p, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_p or want_v):
+            return (None,) * 7
+        up = torch.stack([_f32(g_attr).reshape(()), _f32(g_rep).reshape(())])
+        gp = torch.empty_like(s.grad_points) if want_p else None
+        gv = torch.empty_like(s.grad_verts_attr) if want_v else None
+        _lib.check(_lib.lib().hm_surface_contact_bwd(_lib.ptr(s.grad_points), _lib.ptr(s.inside), _lib.ptr(s.grad_verts_attr),
+                                                     _lib.ptr(s.grad_verts_rep), _lib.ptr(up), s.B * s.N, s.B * s.V,
+                                                     _lib.ptr(gp), _lib.ptr(gv), _lib.stream()), "hm_surface_contact_bwd")
+        return gp, gv, None, None, None, None, None
+
+
+def surface_contact_loss(points, verts, ctx, weights=None, contact_thresh=0.010, collision_thresh=0.020, weight_max=None):
+    """Surface contact loss (csrc/surfcontact.hip, the rules in include/homan_amd.h; beyond the reference): points (B,N,3)
+    against the meshes verts (B,V,3) of ctx's topology -> (A, R), 0-d tensors: attraction = sum over the points OUTSIDE the
+    mesh of w c_a tanh(d / c_a), repulsion = sum over the points INSIDE of c_r tanh(d / c_r), d the exact distance to the
+    surface, both over B N.  weights (N,) fp32 >= 0 weigh the attraction only.  Both `points` and `verts` receive gradients
+    (through the closest point, envelope theorem); results are the same bits from run to run and at any batch position."""
+    _check_surface_inputs(points, verts, ctx)
+    c_a, c_r = _check_surface_thresholds(contact_thresh, collision_thresh)
+    wdev, wmax = ctx.weights(weights, weight_max)
+    return _SurfaceContactLoss.apply(points, verts, ctx, wdev, c_a, c_r, surface_contact_log2q(ctx.N, wmax, c_a, c_r))
+
+
+def surface_contact_terms(points, verts, ctx, weights=None, contact_thresh=0.010, collision_thresh=0.020, weight_max=None):
+    """The per-point detail of `surface_contact_loss`, no gradient -> {"value" (B,N) the point's term u, "bary" (B,N,3) the
+    barycentric weights of its closest point on "face" (B,N) int32, "d2" (B,N), "inside" (B,N) int32, and the call's results
+    "loss" (2,) = (A, R), "grad_points" (B,N,3), "grad_verts_attr", "grad_verts_rep" (B,V,3) at unit upstream}, new tensors."""
+    _check_surface_inputs(points, verts, ctx)
+    c_a, c_r = _check_surface_thresholds(contact_thresh, collision_thresh)
+    wdev, wmax = ctx.weights(weights, weight_max)
+    dev, B, N = ctx.device, ctx.B, ctx.N
+    with torch.no_grad():
+        detail = {"value": torch.empty(B, N, device=dev), "bary": torch.empty(B, N, 3, device=dev),
+                  "d2": torch.empty(B, N, device=dev), "face": torch.empty(B, N, dtype=torch.int32, device=dev)}
+        points = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+        verts = verts.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = _surface_contact_run(points, verts, ctx, wdev, c_a, c_r, surface_contact_log2q(N, wmax, c_a, c_r), detail)
+        detail.update(inside=ctx.inside.clone(), loss=out, grad_points=ctx.grad_points.clone(),
+                      grad_verts_attr=ctx.grad_verts_attr.clone(), grad_verts_rep=ctx.grad_verts_rep.clone())
+    return detail

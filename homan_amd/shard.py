@@ -44,6 +44,9 @@ class ShardStepper:
         self.models, self.shared_scale, self.group, self.hdist = list(models), bool(shared_scale), group, hdist
         if any(getattr(mdl, "sil_mode", "nmr") != "nmr" for mdl in self.models):
             raise NotImplementedError("ShardStepper: sil_mode='soft' clips are not covered by the fused loop")
+        if float(loss_weights.get("lw_surf_attr", 0)) > 0 or float(loss_weights.get("lw_surf_rep", 0)) > 0:
+            raise NotImplementedError("ShardStepper: the surface contact loss (lw_surf_attr / lw_surf_rep) is not covered by the "
+                                      "fused loop (mode='graph' per clip)")
         groups = OrderedDict()
         for i, mdl in enumerate(self.models):
             groups.setdefault(_shape_signature(mdl), []).append(i)
@@ -195,13 +198,16 @@ class ClipFitter:
 
     def __init__(self, loss_weights, num_iterations=400, lr=1e-2, clips_per_batch=1, max_resident=4, class_name="default",
                  hand_proj_mode="persp", optimize_mano=True, optimize_mano_beta=True, optimize_object_scale=False,
-                 image_size=640, mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4):
+                 image_size=640, mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4,
+                 surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all"):
         self.lw, self.steps, self.lr = dict(loss_weights), int(num_iterations), float(lr)
         self.cpb, self.max_resident = max(1, int(clips_per_batch)), max(1, int(max_resident))
         self.model_kw = dict(class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode, optimize_mano=optimize_mano,
                              optimize_mano_beta=optimize_mano_beta, optimize_object_scale=optimize_object_scale,
                              image_size=image_size, mano_model=mano_model, rend_size=rend_size, sync_metrics=False,
-                             ordinal_depth=ordinal_depth, sil_mode=sil_mode, sil_sigma=sil_sigma)
+                             ordinal_depth=ordinal_depth, sil_mode=sil_mode, sil_sigma=sil_sigma,
+                             surface_contact_thresh=surface_contact_thresh, surface_collision_thresh=surface_collision_thresh,
+                             surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones)
         self.resident = OrderedDict()          # (signature, clips) -> FusedStepper
         self._one_by_one = set()          # shape signatures whose clips the fused loop takes one at a time
         self._graph_only = set()          # ... and those it refuses altogether (ortho, free hand scale): the autograd hipGraph

@@ -489,6 +489,55 @@ size_t hm_point_mesh_workspace_bytes(int B, int N, int F);
 int hm_point_mesh_distance(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, float* d2,
                            int* face_idx, int* inside, float* closest, void* workspace, hipStream_t stream);
 
+/* ------------------------------------------------------------------ surface contact loss (csrc/surfcontact.hip)
+ * Attraction of the points outside a mesh and repulsion of the points inside it, each a tanh-saturated exact distance to the
+ * surface (the loss of ObMan, Hasson et al. 2019, on the search above), with both gradients.  Not in the reference tree: the
+ * rules below ARE the definition, pinned bit for bit by the fp32 NumPy restatement of
+ * tests/surfcontact_ref.py.  Every fp32 operation is IEEE without contraction.
+ *
+ * points (B,N,3), verts (B,V,3), faces (F,3) as above; weights (N) fp32 >= 0 or NULL (= 1); c_a = contact_thresh and c_r =
+ * collision_thresh, positive and finite.  The search is hm_point_mesh_distance's: (D, face, inside) per point.  Per point p:
+ *   q, D, the barycentric weights (w0, w1, w2) of q on the winning face (a, b, c), and dv = p - q (world space, as D was formed
+ *   from it) come from ONE walk, the search's own (csrc/surfdist_walk.h), so q and D are the bits of hm_point_mesh_distance:
+ *     A, B, C give a unit weight; AB (1 - t, t, 0), AC (1 - t, 0, t), BC (0, 1 - t, t) with the region's t; the interior
+ *     ((1 - tv) - tw, tv, tw) with tv = vb / s, tw = vc / s; a degenerate face the winning segment's (1 - t, t) on that segment's
+ *     own ends u -> v (ab, bc, ca: ca runs from c to a) and 0 on the third vertex.
+ *   d = sqrtf(D), c = inside ? c_r : c_a, t = hm_tanh(d / c) (csrc/hm_common.h: IEEE double operations, rounded to fp32),
+ *   om = inside ? 1 : weights[i]: the weights belong to the ATTRACTION (a caller restricts attraction to contact zones with
+ *   them; repulsion always counts every point),
+ *   value u = om * (c * t), slope phi = om * (1 - t * t), g[a] = (phi * dv[a]) / d.
+ *   u = 0 and g = 0 when face < 0 (non-finite point, no valid face) or D == 0; the weights are 0 when face < 0.
+ * Losses A = sum over the outside points of u / (B N), R = the same over the inside points: the normaliser is B N for both (not
+ * the count of either set), both vanish at the surface, so A + R is continuous when a point crosses it.
+ * Unit gradients, by the envelope theorem (q minimises the distance over the face: the weights' own derivative drops out):
+ *   grad_points[b,i,a] = (float)((double)g[a] / (B N)), for A if the point is outside and for R if it is inside (`inside` tells);
+ *   grad_verts_attr / grad_verts_rep [b, faces[face][k], a] = sum over the outside / inside points of the fp32 products
+ *   -(w_k * g[a]) (a zero weight adds nothing), / (B N).
+ * Sums are exact: every fp32 addend is rounded to the grid 2^log2q (round to nearest even, in double) and added as a 64-bit
+ * integer count of quanta; the total is converted as (float)(((double)count * 2^log2q) / (double)(B N)).  The loss adds its B
+ * per-frame counts as hi = sum(count >> 32) and lo = sum(count & (2^32 - 1)) and converts (double)hi * 2^32 + (double)lo.  Two
+ * calls return the same bits, and a frame's counts depend neither on B nor on its place in the batch.  No floating-point atomics.
+ * log2q is the caller's: with M = max(max weights, 1) * max(c_a, c_r, 1), which bounds every addend up to rounding,
+ *   log2q = ceil(log2(N M)) - 50
+ * keeps N addends of one frame below 2^51 quanta (exact as a double, and as hm_quant's input): N = 778 points on one face at
+ * unit weights give -40 (ops.surface_contact_log2q).
+ * Outputs: out[2] = (A, R); grad_points (B,N,3); inside (B,N) int32; grad_verts_attr, grad_verts_rep (B,V,3); optional (NULL)
+ * per-point detail value (B,N) = u, bary (B,N,3), d2 (B,N), face_idx (B,N).  workspace: hm_surface_contact_workspace_bytes(B, N,
+ * V, F) bytes, the caller's; the call zeroes what it needs on `stream`.  Every launch goes on `stream`, nothing is allocated or
+ * synchronised: the call can be captured in a hipGraph.  HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: B, N, V or F < 1, a
+ * NULL input, required output or workspace, a threshold that is not positive and finite, |log2q| > 100.
+ * hm_surface_contact_bwd: the autograd backward, upstream (2) fp32 on the device = (dL/dA, dL/dR):
+ *   grad_points[i] = (inside ? upstream[1] : upstream[0]) * unit_points[i]; grad_verts = upstream[0] * unit_verts_attr +
+ *   upstream[1] * unit_verts_rep; either output may be NULL (its inputs are then not read). */
+size_t hm_surface_contact_workspace_bytes(int B, int N, int V, int F);
+int hm_surface_contact_fwd(const float* points, const float* verts, const int* faces, const float* weights, int B, int N, int V,
+                           int F, float contact_thresh, float collision_thresh, int log2q, float* out, float* grad_points,
+                           int* inside, float* grad_verts_attr, float* grad_verts_rep, float* value, float* bary, float* d2,
+                           int* face_idx, void* workspace, hipStream_t stream);
+int hm_surface_contact_bwd(const float* unit_points, const int* inside, const float* unit_verts_attr,
+                           const float* unit_verts_rep, const float* upstream, long n_points, long n_verts, float* grad_points,
+                           float* grad_verts, hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
