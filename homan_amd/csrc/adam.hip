@@ -124,6 +124,7 @@ int hm_adam_step(const void* slots, int n_tensors, int* step, float beta1, float
                  int blocks_per_tensor, hipStream_t stream)
 {
     HM_CHECK_ARG(slots && step && n_tensors > 0 && blocks_per_tensor > 0);
+    HM_CHECK_ARG(HM_ALIGNED(slots, 8));              // the typed void pointer: records of pointers and a long
     hipLaunchKernelGGL(k_adam, dim3(blocks_per_tensor, n_tensors), dim3(256), 0, stream, (const AdamSlot*)slots, n_tensors,
                        step, beta1, beta2, eps, zero_grad, (float*)nullptr, (const float*)nullptr, 0, 0, (float*)nullptr, 0);
     return hm_launch_status();
@@ -135,6 +136,7 @@ int hm_adam_step_log(const void* slots, int n_tensors, int* step, float beta1, f
                      hipStream_t stream)
 {
     HM_CHECK_ARG(slots && step && n_tensors > 0 && blocks_per_tensor > 0);
+    HM_CHECK_ARG(HM_ALIGNED(slots, 8));              // the typed void pointer: records of pointers and a long
     HM_CHECK_ARG(vals && weights && log && n > 0 && nclips > 0);
     hipLaunchKernelGGL(k_adam, dim3(blocks_per_tensor, n_tensors + 1), dim3(256), 0, stream, (const AdamSlot*)slots, n_tensors,
                        step, beta1, beta2, eps, zero_grad, vals, weights, n, max_steps, log, nclips);

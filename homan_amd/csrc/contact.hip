@@ -206,6 +206,7 @@ int hm_nn_fwd_rigid_clips(const float* verts_hand, const float* verts_obj, int B
     HM_CHECK_ARG(!obj_spheres || (obj_rot6d && obj_trans && obj_scale));
     // nn_idx == nn_d2 == NULL: metric only (exact, with pruning of the object-vertex groups that cannot hold the minimum)
     HM_CHECK_ARG(verts_hand && verts_obj && metric_out && workspace && B > 0 && Vh > 0 && Vo > 0 && (!nn_idx == !nn_d2));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(HM_CLIP_LEN_OK(B, clip_len));
     const int nchunk = hm_cdiv(Vh, NN_HV);   // 128 hand vertices per workgroup
     const int Bc = clip_len ? clip_len : B;
@@ -231,6 +232,7 @@ int hm_contact_fwd_clips(const float* verts_hand, const float* verts_obj, const 
                          int out_stride, hipStream_t stream)
 {
     HM_CHECK_ARG(verts_hand && verts_obj && nn_idx && g_hand && g_obj && out1 && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(B > 0 && Vh > 0 && Vo > 0 && HM_CLIP_LEN_OK(B, clip_len));
     const int Bc = clip_len ? clip_len : B;
     HM_CHECK_ARG(Bc <= 512);

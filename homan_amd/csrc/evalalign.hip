@@ -319,6 +319,8 @@ int hm_procrustes_align(const float* pred, const float* gt, int B, int N, int mo
 int hm_threshold_counts(const void* dist, long n, int is_f64, const double* val_max, int steps, void* counts, hipStream_t stream)
 {
     HM_CHECK_ARG(val_max && counts && n >= 0 && n <= (1L << 40) && (dist || n == 0) && steps >= 2 && steps <= EA_MAX_STEPS);
+    // the void pointers: counts are 64-bit words (atomic targets), dist is fp32 or double
+    HM_CHECK_ARG(HM_ALIGNED(counts, 8) && HM_ALIGNED(dist, is_f64 ? 8 : 4));
     const double vmax = *val_max;
     HM_CHECK_ARG(vmax > 0.0 && vmax <= 1.7976931348623157e308);
     const double step = vmax / (double)(steps - 1);

@@ -432,6 +432,7 @@ static int rigid_bwd_launch(const float* mesh, const float* rot6d, const float* 
     HM_CHECK_ARG(mesh && rot6d && scale && g_rot6d && g_trans && N > 0 && V > 0 && HM_CLIP_LEN_OK(N, clip_len));
     HM_CHECK_ARG(n_terms >= 0 && n_terms <= 5 && (n_terms == 0 || (g_terms && weights)));
     HM_CHECK_ARG(!g_frame || frame_stride >= 3);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 8));          // the chunk partials behind the tickets are records of doubles
     RigidTerms t;
     for (int k = 0; k < 5; ++k) { t.p[k] = k < n_terms ? g_terms[k] : nullptr; t.w[k] = k < n_terms ? weights[k] : 0.f; }
     // workspace (hm_rigid_workspace_bytes, zero-filled once): per-frame tickets + chunk partials -> grid (N, chunks);
@@ -506,6 +507,7 @@ int hm_rigid_bwd_sil_clips(const float* mesh, const float* rot6d, const float* s
                            hipStream_t stream)
 {
     HM_CHECK_ARG(sil_parts && adj_off && adj_items && cam_verts && K && F > 0);
+    HM_CHECK_ARG(HM_ALIGNED(sil_parts, 16));         // a face's six doubles are read as three double2 (k_rigid_bwd, k_rigid_bwd_x)
     SilGather sil = {sil_parts, adj_off, adj_items, cam_verts, K, orig_size, F};
     return rigid_bwd_launch(mesh, rot6d, scale, abs_scale, g_terms, weights, n_terms, sil, nullptr, nullptr, 0, 0.f, N, V,
                             nullptr, g_rot6d, g_trans, g_scale_part, workspace, clip_len, 1, sum_log2q,

@@ -37,6 +37,10 @@ static __device__ unsigned long long g_chain_ts[8];
     do {                   \
         if (!(cond)) return HM_ERR_BAD_ARG; \
     } while (0)
+// Alignment contract of include/homan_amd.h (Conventions; audit table in DESIGN.md section 9): a pointer through which a kernel
+// makes an access wider than its element type, and every workspace base, is checked on the host before anything is enqueued.
+// NULL (an optional argument that is absent) passes.
+#define HM_ALIGNED(p, bytes) ((((uintptr_t)(p)) & (uintptr_t)((bytes) - 1)) == 0)
 
 // ---- clip batches (the *_clips entry points) --------------------------------------------------------------------
 // Several independent clips of equal length are optimised by ONE launch per kernel: the frame axis of every per-frame

@@ -299,6 +299,7 @@ int hm_v2d_fwd_clips(const float* verts, const float* camintr, int hand_nb, cons
                      hipStream_t stream)
 {
     HM_CHECK_ARG(verts && camintr && ref2d && unit_grad && out2 && workspace && N > 0 && V > 0 && hand_nb > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(HM_CLIP_LEN_OK(N, clip_len));
     const int Nc = clip_frames(N, clip_len);
     const int nblk = min(HM_RED_MAX_BLOCKS, hm_cdiv((long)Nc * V, RED_THREADS));
@@ -315,6 +316,7 @@ int hm_smooth_fwd_clips(const float* verts, int N, int V, int hand_nb, float* un
                         int clip_len, int out_stride, hipStream_t stream)
 {
     HM_CHECK_ARG(verts && unit_grad && out1 && workspace && N > 0 && V > 0 && hand_nb > 0 && HM_CLIP_LEN_OK(N, clip_len));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     const int Nc = clip_frames(N, clip_len);
     const int nblk = min(HM_RED_MAX_BLOCKS, hm_cdiv((long)Nc * V * 3, RED_THREADS * 4));
     hipLaunchKernelGGL(k_smooth, dim3(nblk, clip_count(N, clip_len)), dim3(RED_THREADS), 0, stream, verts, Nc, V, hand_nb,
@@ -350,6 +352,7 @@ int hm_hand_terms_fwd_clips(const float* verts, const float* camintr, int hand_n
                             void* workspace, int clip_len, int out_stride, hipStream_t stream)
 {
     HM_CHECK_ARG(verts && camintr && ref2d && unit_v2d && out_v2d2 && unit_smooth && out_smooth1 && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(N > 0 && V > 0 && hand_nb > 0 && HM_CLIP_LEN_OK(N, clip_len));
     HM_CHECK_ARG(!pca || (npca > 0 && s_obj && m_obj && s_hand && m_hand && g_pca && g_sobj && g_shand && out_priors3));
     const int Nc = clip_frames(N, clip_len);
@@ -366,6 +369,7 @@ int hm_inter_fwd_clips(const float* verts_hand, const float* verts_obj, const fl
                        int out_stride, hipStream_t stream)
 {
     HM_CHECK_ARG(verts_hand && verts_obj && camintr && frame_rec && out1 && workspace && B > 0 && Vh > 0 && Vo > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(HM_CLIP_LEN_OK(B, clip_len));
     hipLaunchKernelGGL(k_inter, dim3(B), dim3(RED_THREADS), 0, stream, verts_hand, verts_obj, camintr, B, Vh, Vo,
                        expansion, zthresh, frame_rec, ws_counter(workspace), out1, clip_frames(B, clip_len), out_stride);

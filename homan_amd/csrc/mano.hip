@@ -659,6 +659,7 @@ int hm_mano_fwd_rows(const void* const* model, const float* pca, int pca_dim, co
     HM_CHECK_ARG(model && pca && rot && betas && verts && B > 0 && pca_dim >= 16 && row_stride >= 1 && row0 >= 0 && row0 < row_stride);
     HM_CHECK_ARG(clip_len >= 0 && (clip_len == 0 || (B * row_stride) % clip_len == 0));
     HM_CHECK_ARG(!verts_world || (rigid_rot6d && rigid_trans && rigid_scale));
+    HM_CHECK_ARG(HM_ALIGNED(model[4], 16));          // lbs_weights rows are read as float4 (mano_skin_transform)
     ManoModelDev m = {(const float*)model[0], (const float*)model[1], (const float*)model[2], (const float*)model[3],
                       (const float*)model[4], (const float*)model[5], (const float*)model[6], (const int*)model[7]};
     hipLaunchKernelGGL(k_mano_fwd, dim3(MANO_NCH64, (B + MANO_FPW - 1) / MANO_FPW), dim3(256), 0, stream, m, pca, pca_dim, rot, betas, trans, B, verts,
@@ -673,6 +674,7 @@ int hm_mano_fwd_clips(const void* const* model, const float* pca, int pca_dim, c
 {
     HM_CHECK_ARG(model && pca && rot && betas && verts && B > 0 && pca_dim >= 16 && HM_CLIP_LEN_OK(B, clip_len));
     HM_CHECK_ARG(!verts_world || (rigid_rot6d && rigid_trans && rigid_scale));
+    HM_CHECK_ARG(HM_ALIGNED(model[4], 16));          // lbs_weights rows are read as float4 (mano_skin_transform)
     ManoModelDev m = {(const float*)model[0], (const float*)model[1], (const float*)model[2], (const float*)model[3],
                       (const float*)model[4], (const float*)model[5], (const float*)model[6], (const int*)model[7]};
     hipLaunchKernelGGL(k_mano_fwd, dim3(MANO_NCH64, (B + MANO_FPW - 1) / MANO_FPW), dim3(256), 0, stream, m, pca, pca_dim, rot, betas, trans, B, verts,
@@ -696,7 +698,9 @@ static int mano_bwd_launch(const void* const* model, const float* pca, int pca_d
                            const ManoRigid& mr, hipStream_t stream)
 {
     HM_CHECK_ARG(model && pca && rot && betas && (g_verts || mr.mesh) && g_pca && g_rot && g_betas && g_trans && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // 32-bit tickets (atomic targets), then fp32 partial sums
     HM_CHECK_ARG(B > 0 && pca_dim >= 16 && row_stride >= 1 && row0 >= 0 && row0 < row_stride);
+    HM_CHECK_ARG(HM_ALIGNED(model[4], 16));          // lbs_weights rows are read as float4 (mano_skin_transform)
     ManoModelDev m = {(const float*)model[0], (const float*)model[1], (const float*)model[2], (const float*)model[3],
                       (const float*)model[4], (const float*)model[5], (const float*)model[6], (const int*)model[7]};
     unsigned int* cnt = (unsigned int*)workspace;

@@ -160,6 +160,7 @@ int hm_mask_crop_resize(const void* masks, int masks_f32, int N, int H, int W, c
     HM_CHECK_ARG(R >= 0 && S > 0 && S <= 4096 && N > 0 && H > 0 && W > 0 && (long)H * W <= 0x7fffffffL);
     if (R == 0) return HM_OK;
     HM_CHECK_ARG(masks && boxes && out);
+    HM_CHECK_ARG(!masks_f32 || HM_ALIGNED(masks, 4));                 // the void pointer: bytes or fp32
     for (int r0 = 0; r0 < R; r0 += MC_MAX_GRID_Y) {
         const int nr = min(R - r0, MC_MAX_GRID_Y);
         hipLaunchKernelGGL(k_mask_crop_resize, dim3(hm_cdiv((long)S * S, MC_THREADS), nr), dim3(MC_THREADS), 0, stream, masks,
@@ -176,6 +177,7 @@ int hm_target_masks(int mode, const void* target, int target_f32, int Nt, const 
                  (long)H * W <= 0x7fffffffL);
     if (R == 0) return HM_OK;
     HM_CHECK_ARG(target && boxes && out && (K == 0 || (occluders && occluder_index && No > 0)));
+    HM_CHECK_ARG((!target_f32 || HM_ALIGNED(target, 4)) && (!occluders_f32 || HM_ALIGNED(occluders, 4)));      // void: bytes or fp32
     for (int r0 = 0; r0 < R; r0 += MC_MAX_GRID_Y) {
         const int nr = min(R - r0, MC_MAX_GRID_Y);
         hipLaunchKernelGGL(k_target_masks, dim3(hm_cdiv((long)S * S, MC_THREADS), nr), dim3(MC_THREADS), 0, stream, mode, target,

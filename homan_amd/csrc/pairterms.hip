@@ -84,6 +84,7 @@ int hm_pair_terms_fwd_clips(const float* verts_hand, const float* verts_obj, con
     HM_CHECK_ARG(!obj_spheres || (obj_rot6d && obj_trans && obj_scale));
     HM_CHECK_ARG(verts_hand && verts_obj && B > 0 && Vh > 0 && Vo > 0 && HM_CLIP_LEN_OK(B, clip_len));
     HM_CHECK_ARG(metric_out || out_inter || out_smooth || ht_out_v2d2);
+    HM_CHECK_ARG(HM_ALIGNED(ws_nn, 4) && HM_ALIGNED(ws_inter, 4) && HM_ALIGNED(ws_smooth, 4) && HM_ALIGNED(ws_hand, 4));      // reduce workspaces
     HM_CHECK_ARG(!ht_out_v2d2 || (ht_ref2d && ht_unit_v2d && ht_unit_smooth && ht_out_smooth1 && ws_hand && camintr));
     HM_CHECK_ARG(!ht_pca || (ht_npca > 0 && ht_s_obj && ht_m_obj && ht_s_hand && ht_m_hand && ht_g_pca && ht_g_sobj &&
                              ht_g_shand && ht_out_priors3));

@@ -244,6 +244,7 @@ int hm_cloud_metrics(const float* x, const float* y, int B, int N, int M, const 
                      int* x_idx, float* y_d2, int* y_idx, double* out4, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(x && y && out4 && workspace && B > 0 && N > 0 && M > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 8));          // double partial sums
     const int nblk = hm_cdiv(N, NN_HV) + hm_cdiv(M, NN_HV);
     for (int b0 = 0; b0 < B; b0 += PM_MAX_GRID_Y) {      // the frame axis in launches of at most 65535 frames
         const int nb = min(B - b0, PM_MAX_GRID_Y);

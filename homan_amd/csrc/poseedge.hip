@@ -240,6 +240,7 @@ int hm_pose_edge_terms(const float* alpha, const float* keep, const float* ref, 
                        int kernel_size, float lw_chamfer, float* terms, float* grad, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(alpha && keep && ref && edt && terms && grad && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // 32-bit tickets (atomic targets), then fp32 partial sums
     HM_CHECK_ARG(N > 0 && N <= 65535 && size > 0 && stride >= size);
     if (kernel_size < 3 || kernel_size > 2 * PE_R + 1 || kernel_size % 2 == 0) return HM_ERR_UNSUPPORTED;
     unsigned int* tickets = static_cast<unsigned int*>(workspace);

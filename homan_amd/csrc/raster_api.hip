@@ -117,6 +117,10 @@ int hm_sil_fwd_phase_clips(const float* verts, const int* faces, int faces_bstri
 {
     HM_CHECK_ARG(phases >= 1 && phases <= 3);
     HM_CHECK_ARG(verts && faces && K && pooled && workspace && HM_CLIP_LEN_OK(B, clip_len));
+    // alignment contract: the workspace's carve-outs hold uint4 records; alpha_full is written, and the per-sample loss reads
+    // keep / ref, as float2 (k_raster_fwd)
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN) && HM_ALIGNED(alpha_full, 8));
+    HM_CHECK_ARG(!(keep && ref && (alpha_full || (mask_shared & 2))) || (HM_ALIGNED(keep, 8) && HM_ALIGNED(ref, 8)));
     if (clip_len == 0) clip_len = B;
     HM_CHECK_ARG(!rigid_rot6d || (rigid_trans && rigid_scale));
     HM_CHECK_ARG(B > 0 && V > 0 && F > 0 && S > 0);
@@ -180,6 +184,7 @@ int hm_sil_fwd_multi(const HmSilRender* renders, int n, int phases, hipStream_t 
     for (int g = 0; g < n; ++g) {
         const HmSilRender& r = renders[g];
         HM_CHECK_ARG(r.verts && r.faces && r.K && r.pooled && r.workspace && HM_CLIP_LEN_OK(r.B, r.clip_len));
+        HM_CHECK_ARG(HM_ALIGNED(r.workspace, HM_SIL_WS_ALIGN));
         HM_CHECK_ARG(!r.rigid_rot6d || (r.rigid_trans && r.rigid_scale));
         HM_CHECK_ARG(r.B > 0 && r.V > 0 && r.F > 0 && r.S > 0 && (!r.keep == !r.ref));
         if (r.S % 16 != 0 || 2 * r.S > 8192 || 2L * r.F >= (1L << 30) || r.B >= 32768) return HM_ERR_UNSUPPORTED;
@@ -209,6 +214,7 @@ int hm_sil_fwd_multi(const HmSilRender* renders, int n, int phases, hipStream_t 
 int hm_sil_hint_near_winding(void* workspace, int winding, hipStream_t stream)
 {
     HM_CHECK_ARG(workspace && (winding == 0 || winding == 1));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     return hipMemsetAsync((char*)workspace + 24 * 4, winding, 1, stream) == hipSuccess ? HM_OK : HM_ERR_LAUNCH;
 }
 
@@ -219,6 +225,7 @@ int hm_sil_reduce_clips(int B, int V, int F, int S, const float* keep_sum, float
                         void* workspace, int clip_len, int out_stride, hipStream_t stream)
 {
     HM_CHECK_ARG(workspace && B > 0 && S > 0 && (frame_out || loss_out) && (!loss_out || keep_sum));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     HM_CHECK_ARG(HM_CLIP_LEN_OK(B, clip_len));
     SilWs w = carve(workspace, B, V, F, S);
     hm_launch_sil_reduce(w, B, S, keep_sum, loss_out, frame_out, clip_len ? clip_len : B, out_stride, stream);
@@ -251,6 +258,8 @@ int hm_sil_bwd_phase_clips(const float* verts, const float* K, int B, int V, int
     HM_CHECK_ARG(!loss_out || ((mode == 1 || mode == 2) && keep_sum));
     HM_CHECK_ARG(sum_log2q <= 0 && sum_log2q >= -60);
     HM_CHECK_ARG(verts && K && adj_off && adj_items && workspace);        // grad_verts == NULL: no vertex gather (see hm_sil_parts)
+    // alignment contract: mode 3 reads grad_pooled as float2 (k_bwd_masks)
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN) && (mode != 3 || HM_ALIGNED(grad_pooled, 8)));
     HM_CHECK_ARG(HM_CLIP_LEN_OK(B, clip_len));
     if (clip_len == 0) clip_len = B;
     HM_CHECK_ARG((mode == 0 || mode == 3) ? grad_pooled != nullptr : ((mode == 4 || mode == 5) ? upstream != nullptr : (upstream && keep_sum)));
@@ -287,6 +296,7 @@ int hm_sil_bwd(const float* verts, const float* K, int B, int V, int F, int S, f
 // grid 2^sum_log2q, see hm_quant): input of hm_rigid_bwd_sil.
 const double* hm_sil_parts(const void* workspace, int B, int V, int F, int S)
 {
+    if (!workspace || !HM_ALIGNED(workspace, HM_SIL_WS_ALIGN)) return nullptr;      // (the alignment contract: no code to return here)
     return carve((void*)workspace, B, V, F, S).parts;
 }
 
@@ -298,6 +308,7 @@ int hm_shade_rgb(const float* verts, const int* faces, int faces_bstride, const 
                  float* rgb, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(verts && faces && textures && light_dir && background && rgb && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     HM_CHECK_ARG(B > 0 && V > 0 && F > 0 && S > 0);
     SilWs w = carve(workspace, B, V, F, S);
     hm_launch_shade_rgb(w, verts, faces, faces_bstride, textures, B, V, F, S, light_dir, intensity_ambient, intensity_directional,
@@ -317,6 +328,7 @@ int hm_bench_sil_kernels(const float* verts, const int* faces, const float* K, i
                          hipStream_t stream)
 {
     HM_CHECK_ARG(verts && faces && K && keep && ref && keep_sum && pooled && loss_out && workspace && reps > 0 && avg_ms);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     HM_CHECK_ARG(adj_off && adj_items && upstream && grad_verts);
     int rc = hm_sil_fwd(verts, faces, 0, K, B, V, F, S, 1.0f, 0.1f, 100.0f, keep, ref, keep_sum, pooled, loss_out,
                         work_order, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, workspace, stream);
@@ -371,6 +383,7 @@ size_t hm_sil_timestamps_bytes(int B, int V, int F, int S) { (void)V; return ts_
 int hm_sil_timestamps(void* workspace, int B, int V, int F, int S, int enable, hipStream_t stream)
 {
     HM_CHECK_ARG(workspace && B > 0 && F > 0 && S > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve(workspace, B, V, F, S);
     if (hipMemsetAsync((char*)workspace + 24 * 4 + 1, enable ? 1 : 0, 1, stream) != hipSuccess) return HM_ERR_LAUNCH;
     if (enable && hipMemsetAsync(w.ts, 0, ts_units(B, F, S) * 16, stream) != hipSuccess) return HM_ERR_LAUNCH;
@@ -379,12 +392,14 @@ int hm_sil_timestamps(void* workspace, int B, int V, int F, int S, int enable, h
 int hm_sil_timestamps_save(const void* workspace, int B, int V, int F, int S, void* dst, hipStream_t stream)
 {
     HM_CHECK_ARG(workspace && dst);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(dst, w.ts, ts_units(B, F, S) * 16, hipMemcpyDeviceToDevice, stream) == hipSuccess ? HM_OK : HM_ERR_LAUNCH;
 }
 int hm_sil_timestamps_read(const void* workspace, int B, int V, int F, int S, const void* saved, float* us3, hipStream_t stream)
 {
     HM_CHECK_ARG((workspace || saved) && us3 && B > 0 && F > 0 && S > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     const size_t n = ts_units(B, F, S);
     unsigned long long* t = (unsigned long long*)malloc(n * 16);
     if (!t) return HM_ERR_LAUNCH;
@@ -420,24 +435,28 @@ int hm_debug_sweep_caps(int cap)
 // debug / test access to forward intermediates held in the workspace
 int hm_sil_read_idx_map(const void* workspace, int B, int V, int F, int S, int* out, hipStream_t stream)
 {
+    HM_CHECK_ARG(workspace && out && HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.idx_map, (size_t)B * 4 * S * S * 4, hipMemcpyDeviceToDevice, stream) == hipSuccess
                ? HM_OK : HM_ERR_LAUNCH;
 }
 int hm_sil_read_boxes(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream)
 {
+    HM_CHECK_ARG(workspace && out && HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.boxes, (size_t)B * F * 8, hipMemcpyDeviceToDevice, stream) == hipSuccess ? HM_OK
                                                                                                          : HM_ERR_LAUNCH;
 }
 int hm_sil_read_owned(const void* workspace, int B, int V, int F, int S, void* out, hipStream_t stream)
 {
+    HM_CHECK_ARG(workspace && out && HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.owned, (size_t)B * F * 2, hipMemcpyDeviceToDevice, stream) == hipSuccess ? HM_OK
                                                                                                          : HM_ERR_LAUNCH;
 }
 int hm_sil_read_faces9(const void* workspace, int B, int V, int F, int S, float* out, hipStream_t stream)
 {
+    HM_CHECK_ARG(workspace && out && HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.faces9, (size_t)B * F * 9 * 4, hipMemcpyDeviceToDevice, stream) == hipSuccess
                ? HM_OK : HM_ERR_LAUNCH;
@@ -448,12 +467,14 @@ int hm_sil_read_faces9(const void* workspace, int B, int V, int F, int S, float*
 int hm_sil_invalidate_outputs(void* workspace, int B, int V, int F, int S, hipStream_t stream)
 {
     HM_CHECK_ARG(workspace && B > 0 && S > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve(workspace, B, V, F, S);
     return hipMemsetAsync(w.region_state, 0, (size_t)B * (S / 16) * (S / 16), stream) == hipSuccess ? HM_OK : HM_ERR_LAUNCH;
 }
 // (B,F,3,2) doubles: the per-(face, corner) sums of the last backward (tests: compared bit for bit with the CPU oracle)
 int hm_sil_read_parts(const void* workspace, int B, int V, int F, int S, double* out, hipStream_t stream)
 {
+    HM_CHECK_ARG(workspace && out && HM_ALIGNED(workspace, HM_SIL_WS_ALIGN));
     SilWs w = carve((void*)workspace, B, V, F, S);
     return hipMemcpyAsync(out, w.parts, (size_t)B * F * 6 * 8, hipMemcpyDeviceToDevice, stream) == hipSuccess
                ? HM_OK : HM_ERR_LAUNCH;

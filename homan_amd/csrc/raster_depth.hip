@@ -357,6 +357,8 @@ int hm_depth_bwd_sparse(const float* verts, const float* K, int B, int V, int F,
 {
     HM_CHECK_ARG(verts && K && grad_pooled_depth && adj_off && adj_items && grad_verts && workspace);
     HM_CHECK_ARG(!gflags || S % 64 == 0);
+    // alignment contract: the gather scans the flag bytes four at a time (k_depth_bwd_gather)
+    HM_CHECK_ARG(HM_ALIGNED(workspace, HM_SIL_WS_ALIGN) && HM_ALIGNED(gflags, 4));
     if (S % 16 != 0) return HM_ERR_UNSUPPORTED;
     SilWs w = carve(workspace, B, V, F, S);
     hipLaunchKernelGGL(k_depth_bwd_faces, dim3(hm_cdiv(hm_cdiv((long)B * F, DBF_FACES) * 64, 256)), dim3(256), 0, stream, w.faces9, w.boxes,
@@ -380,6 +382,7 @@ int hm_ordinal_depth_fwd(const float* d0, const float* d1, const float* a0, cons
                          void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(d0 && d1 && a0 && a1 && m0 && m1 && frame_part && rec && out1 && workspace && B > 0 && S > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // reduce workspace: fp32 partials and a 32-bit ticket
     HM_CHECK_ARG(S <= 1024 && ((uintptr_t)frame_part & 7) == 0);
     hipLaunchKernelGGL(k_ordinal_depth, dim3(ORD_CHUNKS, B), dim3(256), 0, stream, d0, d1, a0, a1, m0, m1, B, S, frame_part,
                        (unsigned int*)((float*)workspace + 512), rec, out1);

@@ -28,7 +28,10 @@ static inline size_t ts_units(int B, int F, int S) { return ts_raster_units(B, S
 static inline size_t sweep_ucap(int B, int F) { return (size_t)B * F * 4 + 1024; }
 static inline size_t sweep_slot_cap(int B, int F) { return sweep_ucap(B, F) + (size_t)B * F; }
 
-// workspace layout helper (bytes), all chunks 256-byte aligned
+// workspace layout helper (bytes), all chunks 256-byte aligned RELATIVE TO THE BASE; the widest access into a chunk is 16 bytes
+// (uint4 line records, the float4 loss partials, the 16-byte plane stores), so that is what the base must be aligned to: every
+// entry point that carves checks it (HM_SIL_WS_ALIGN)
+#define HM_SIL_WS_ALIGN 16
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // face bins of a render of S^2 pixels (raster_common.h): the bins a frame of that size really has - 0 without bins -, their
 // counters (+ one ticket word per super-region; a region bin has none) and their lists of F entries, the safe worst case

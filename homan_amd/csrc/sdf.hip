@@ -419,6 +419,7 @@ int hm_collision_fwd_clips(const float* verts0, const int* faces0, int V0, int F
 {
     HM_CHECK_ARG(verts0 && faces0 && verts1 && faces1 && g0 && g1 && out1 && workspace);
     HM_CHECK_ARG(B > 0 && V0 > 0 && V1 > 0 && F0 > 0 && F1 > 0 && HM_CLIP_LEN_OK(B, clip_len));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 16));         // the triangle records are written and read as float4
     CollWs w;
     coll_layout(workspace, B, V0, V1, F0, F1, &w);
     hipLaunchKernelGGL(k_sdf_boxes, dim3(B, 2), dim3(SDF_THREADS), 0, stream, verts0, V0, verts1, V1, B, scale_factor,
@@ -450,6 +451,7 @@ int hm_collision_dist_values(const float* verts0, int V0, const float* verts1, i
                              float* dv1, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(verts0 && verts1 && dv0 && dv1 && workspace && B > 0 && V0 > 0 && V1 > 0);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 16));
     CollWs w;
     coll_layout(workspace, B, V0, V1, F0, F1, &w);
     const int chunks = hm_cdiv(V0 > V1 ? V0 : V1, SDF_THREADS);
@@ -463,6 +465,7 @@ int hm_collision_read_grid(const int* faces, int V, int F, int B, int which, int
                            void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(faces && phi && workspace && (which == 0 || which == 1));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 16));
     CollWs w;
     coll_layout(workspace, B, V0, V1, F0, F1, &w);
     hipLaunchKernelGGL(k_sdf_grid, dim3(SDF_N * SDF_N * SDF_N / SDF_THREADS, B), dim3(SDF_THREADS), 0, stream,
@@ -477,6 +480,7 @@ int hm_collision_read_needed(int B, int which, int V0, int V1, int F0, int F1, v
                              void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(need_mask && need_len && phi && workspace && B > 0 && (which == 0 || which == 1));
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 16));
     CollWs w;
     coll_layout(workspace, B, V0, V1, F0, F1, &w);
     const size_t rows = (size_t)SDF_N * SDF_N, grid = rows * SDF_N;

@@ -52,6 +52,7 @@ int hm_keyframe_interp(const float* key_vals, const int* key_frames, int K, int 
     HM_CHECK_ARG(key_vals && key_frames && signs && key_frames_dev && out && K > 0 && N > 0 && frame_nb > 0);
     HM_CHECK_ARG(gather ? (gather_dev && M > 0) : M == N);
     HM_CHECK_ARG(M <= 0x7fffffff / 3 - KI_THREADS);
+    HM_CHECK_ARG(HM_ALIGNED(out, out_f64 ? 8 : 4));  // the void pointer: fp32 or double elements
     HM_CHECK_ARG(key_frames[0] == 0 && key_frames[K - 1] <= frame_nb);
     for (int k = 1; k < K; ++k) HM_CHECK_ARG(key_frames[k] > key_frames[k - 1]);
     for (int i = 0; gather && i < M; ++i) HM_CHECK_ARG(gather[i] >= 0 && gather[i] < N);

@@ -137,6 +137,7 @@ int hm_softsil_pose_terms(const float* alpha, const float* keep, const float* re
                           void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(alpha && keep && ref && terms && grad && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // 32-bit tickets (atomic targets), then fp32 partial sums
     HM_CHECK_ARG(N >= 1 && N <= 65535 && S >= 1 && S <= SP_MAX_SIZE);
     const long npix = (long)S * S;
     unsigned int* tickets = static_cast<unsigned int*>(workspace);

@@ -267,6 +267,7 @@ extern "C" int hm_softsil_fwd(const float* verts, const int* faces, const float*
                               float znear, float zfar, const float* sigma, float* alpha, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(verts && faces && K && sigma && alpha && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // face records and partial sums of 4-byte members
     HM_CHECK_ARG(softsil_shape_ok(B, V, F, S) && orig_size > 0.0f && znear < zfar);
     SoftFace* rec = (SoftFace*)workspace;
     const long BF = (long)B * F;
@@ -284,6 +285,7 @@ extern "C" int hm_softsil_bwd(const float* verts, const int* faces, const float*
                               const int* adj_off, const int* adj_items, float* grad_verts, void* workspace, hipStream_t stream)
 {
     HM_CHECK_ARG(verts && faces && K && sigma && alpha && grad_alpha && adj_off && adj_items && grad_verts && workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 4));          // face records and partial sums of 4-byte members
     HM_CHECK_ARG(softsil_shape_ok(B, V, F, S) && orig_size > 0.0f && znear < zfar);
     SoftFace* rec = (SoftFace*)workspace;
     float* parts = (float*)((char*)workspace + softsil_parts_offset(B, F));

@@ -173,6 +173,7 @@ int hm_solid_voxels(const float* verts, const int* faces, int B, int V, int F, f
     HM_CHECK_ARG(verts && faces && boxes && boxes_dev && B > 0 && V > 0 && F > 0);
     HM_CHECK_ARG(pitch > 0.0f && pitch <= 3.4028234e38f);          // (a NaN fails the first comparison)
     HM_CHECK_ARG(NWX >= 0 && NY >= 0 && NZ >= 0);
+    HM_CHECK_ARG(HM_ALIGNED(words, 4));              // the void pointer: 32-bit words (atomic targets)
     for (long b = 0; b < B; ++b) {
         const int* bx = boxes + b * 6;
         HM_CHECK_ARG(bx[3] >= 0 && bx[4] >= 0 && bx[5] >= 0);
@@ -201,6 +202,7 @@ int hm_solid_voxels(const float* verts, const int* faces, int B, int V, int F, f
 int hm_voxel_overlap(const void* a, int a_sets, const void* b, int B, long words_per_frame, void* counts, hipStream_t stream)
 {
     HM_CHECK_ARG(counts && a_sets > 0 && B > 0 && words_per_frame >= 0 && (words_per_frame == 0 || (a && b)));
+    HM_CHECK_ARG(HM_ALIGNED(counts, 8) && HM_ALIGNED(a, 4) && HM_ALIGNED(b, 4));      // the void pointers: 64-bit counts, 32-bit words
     hipLaunchKernelGGL(k_voxel_overlap, dim3(B), dim3(SV_THREADS), 0, stream, (const unsigned int*)a, a_sets,
                        (const unsigned int*)b, (long)B, words_per_frame, (unsigned long long*)counts);
     return hm_launch_status();

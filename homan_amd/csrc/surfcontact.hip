@@ -173,6 +173,7 @@ int hm_surface_contact_fwd(const float* points, const float* verts, const int* f
     HM_CHECK_ARG(contact_thresh > 0.f && collision_thresh > 0.f && contact_thresh <= 3.4028234e38f &&
                  collision_thresh <= 3.4028234e38f);         // (a NaN fails)
     HM_CHECK_ARG(log2q >= -100 && log2q <= 100);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 8));          // 64-bit accumulator words, the targets of integer atomics, at its base
     const size_t acc_bytes = sc_acc_words(B, V) * sizeof(sc_word);
     sc_word* acc = (sc_word*)workspace;
     sc_word* acc_attr = acc;

@@ -149,6 +149,7 @@ int hm_point_mesh_distance(const float* points, const float* verts, const int* f
     int per;
     const int splits = sd_splits(B, N, F, &per);
     HM_CHECK_ARG(splits == 1 || workspace);
+    HM_CHECK_ARG(HM_ALIGNED(workspace, 8));          // 64-bit (distance, face) words, the targets of atomicMin, at its base
     const long total = (long)B * N;                 // every index of the kernels is a 64-bit product of the int sizes
     unsigned long long* ws_min = (unsigned long long*)workspace;
     unsigned int* ws_par = splits > 1 ? (unsigned int*)(ws_min + total) : nullptr;

@@ -114,6 +114,16 @@ def ptr(t):
     return t.data_ptr()
 
 
+def aligned(t, nbytes):
+    """`t` itself when its address is a multiple of `nbytes`, else an equal copy in an allocation of its own (torch's allocators
+    hand out far more than 16 bytes of alignment).  For caller-supplied tensors that go to a parameter whose alignment
+    requirement exceeds the element size (include/homan_amd.h, Conventions): a contiguous view such as `x.view(-1)[1:1 + n]` is
+    only element-aligned.  Buffers this package allocates itself need nothing."""
+    if t is None or t.data_ptr() % nbytes == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream
 

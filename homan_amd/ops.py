@@ -279,7 +279,7 @@ class _SilhouetteRenderNoAA(torch.autograd.Function):
     def backward(ctx, g_img):
         verts, K = ctx.saved_tensors
         sctx = ctx.sctx
-        g_img = sctx.pad_samples(_f32(g_img))
+        g_img = _lib.aligned(sctx.pad_samples(_f32(g_img)), 8)         # (mode 3 reads it as float2)
         grad_verts = torch.empty_like(verts)
         _lib.check(sctx.backward(verts, K, 3, grad_pooled=g_img, grad_verts=grad_verts, orig_size=ctx.orig_size), "hm_sil_bwd")
         return grad_verts, None, None, None
@@ -301,6 +301,7 @@ class _MaskedSilhouetteL2NoAA(torch.autograd.Function):
         n = 2 * sctx.S
         keep, ref = sctx.pad_samples(keep), sctx.pad_samples(ref)      # (padding: keep = 0, it counts for nothing)
         assert keep.shape == (n, n) and ref.shape == (n, n) and keep.is_contiguous() and ref.is_contiguous()
+        keep, ref = _lib.aligned(keep, 8), _lib.aligned(ref, 8)        # (the per-sample loss reads them as float2)
         pooled = torch.empty(sctx.B, sctx.S, sctx.S, device=verts.device)
         alpha = torch.empty(sctx.B, n, n, device=verts.device)
         frame = torch.empty(sctx.B, 2, device=verts.device)

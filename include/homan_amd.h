@@ -18,7 +18,16 @@
  *     entry point is called or captured - a thread sets them, issues or captures its launches, restores them; threads do not
  *     see each other's values; and the process-wide hm_debug_* hooks (timing events, capacity overrides: test tools);
  *   - workspaces that hold a reduction ticket (hm_reduce_workspace_bytes, hm_sil_workspace_bytes,
- *     hm_collision_workspace_bytes) must be zero-filled ONCE before first use; the ticket resets itself.
+ *     hm_collision_workspace_bytes) must be zero-filled ONCE before first use; the ticket resets itself;
+ *   - ALIGNMENT.  A pointer must be aligned to its element type: 4 bytes for fp32 / int32, 8 for double and for 64-bit words,
+ *     1 for bytes; a `void*` that stands for typed elements (stated at the entry point) to that type.  A contiguous view into a
+ *     larger buffer satisfies this and nothing more.  Where a kernel makes a wider access through a caller's pointer, the entry
+ *     point's comment names the parameter and the bytes ("ALIGNMENT: ..."), and every workspace states the alignment of its base
+ *     (4, 8 or 16 bytes; what *_workspace_bytes returns is exact, nothing is touched outside it).  A pointer that violates an
+ *     ALIGNMENT note, a misaligned workspace base, or a misaligned typed `void*` is refused with HM_ERR_BAD_ARG before anything
+ *     is enqueued, set or copied: every access wider than its element type that a kernel makes through a caller's pointer is
+ *     covered by such a note and such a check.  NULL optional arguments pass.  The
+ *     audit behind the notes (parameter, bytes, kernel and line) is the table of DESIGN.md section 9.
  *
  * `hipStream_t` is declared as an opaque pointer so that the header is usable from plain C hosts (ctypes, cgo...).
  */
@@ -57,7 +66,10 @@ int hm_rigid_bwd(const float* mesh, const float* rot6d, const float* scale, int 
                  float frame_scale, int N, int V, float* g_mesh, float* g_rot6d, float* g_trans, float* g_scale_part,
                  void* workspace, hipStream_t stream);
 /* workspace of hm_rigid_bwd / hm_rigid_bwd_sil (zero-filled once; per-frame tickets reset themselves): with it the frame
- * is split over ceil(V/256) workgroups and the last one finishes; NULL = one workgroup per frame. */
+ * is split over ceil(V/256) workgroups and the last one finishes; NULL = one workgroup per frame.
+ * ALIGNMENT: workspace base 8 bytes (records of doubles behind the tickets), every hm_rigid_bwd* entry; sil_parts 16 bytes in
+ * hm_rigid_bwd_sil and hm_rigid_bwd_sil_clips (a face's six doubles are read as three 16-byte pairs; what hm_sil_parts returns
+ * for a conforming workspace is so aligned). */
 size_t hm_rigid_workspace_bytes(int N);
 /* hm_rigid_bwd with the silhouette gradient as one more full term, gathered on the fly from the per-(face, corner) NDC
  * gradients of the edge sweeps (sil_parts = hm_sil_parts(workspace) after an hm_sil_bwd called with grad_verts == NULL;
@@ -111,7 +123,7 @@ int hm_edge_edt(const float* ref, int size, int stride, int kernel_size, float p
  *   sample, in row-major order of the window clipped to the image, that holds the window's maximum (an all-zero window
  *   names its top-left sample).  Fixed summation order, no floating-point atomics: two calls agree bit for bit.
  *   kernel_size odd, 3..7, else HM_ERR_UNSUPPORTED; N <= 65535.  workspace: hm_pose_edge_workspace_bytes(N, stride) bytes,
- *   zero-filled once (self-resetting tickets). */
+ *   zero-filled once (self-resetting tickets).  ALIGNMENT: workspace base 4 bytes. */
 size_t hm_pose_edge_workspace_bytes(int N, int stride);
 int hm_pose_edge_terms(const float* alpha, const float* keep, const float* ref, const float* edt, int N, int size, int stride,
                        int kernel_size, float lw_chamfer, float* terms, float* grad, void* workspace, hipStream_t stream);
@@ -127,11 +139,12 @@ int hm_scale_by(const float* in, const float* s, long n, float* out, hipStream_t
  *   trans (B,3) or NULL.  verts (B,778,3); joints (B,16,3) optional.
  *   verts_world (B,778,3) optional: the rigid hand transform of hm_rigid_fwd (rigid_rot6d (B,3,2), rigid_trans (B,3),
  *   rigid_scale (1), no abs) applied in the same launch.
- *   state (hm_mano_state_bytes(B)) optional: kinematic-chain state + posed vertices kept for hm_mano_bwd. */
+ *   state (hm_mano_state_bytes(B)) optional: kinematic-chain state + posed vertices kept for hm_mano_bwd.
+ *   ALIGNMENT: model[4] (lbs_weights) 16 bytes - its rows of 16 weights are read as four float4 - in every hm_mano_* entry. */
 int hm_mano_fwd(const void* const* model, const float* pca, int pca_dim, const float* rot, const float* betas,
                 const float* trans, int B, float* verts, float* joints, const float* rigid_rot6d, const float* rigid_trans,
                 const float* rigid_scale, float* verts_world, float* state, hipStream_t stream);
-size_t hm_mano_workspace_bytes(int B);      /* zero-filled once by the caller (self-resetting per-frame tickets) */
+size_t hm_mano_workspace_bytes(int B);      /* zero-filled once by the caller (self-resetting per-frame tickets); ALIGNMENT: base 4 bytes */
 size_t hm_mano_state_bytes(int B);
 /* g_pca_extra (B,pca_dim) optional: g_pca = d/d pca through the mesh + w_extra * g_pca_extra (e.g. the PCA prior).
  * state: what hm_mano_fwd stored for the SAME parameters, or NULL (the chain is then recomputed). */
@@ -177,7 +190,11 @@ int hm_mano_bwd_rigid_clips(const void* const* model, const float* pca, int pca_
  *   persistent_outputs != 0: the caller passes the SAME pooled / pooled_depth / keep / ref buffers as in the previous call on
  *     this workspace (a fixed optimisation loop); regions that were background then and are background now are not
  *     rewritten.  0 = every output is written.
- *   S must be a multiple of 16 (32 and <= 512 for the silhouette backward). */
+ *   S must be a multiple of 16 (32 and <= 512 for the silhouette backward).
+ *   ALIGNMENT (hm_sil_fwd and its _clips / _phase_clips / _multi forms): workspace base 16 bytes, in every entry point that takes
+ *     this workspace (every hm_sil_*, hm_depth_bwd*, hm_shade_rgb, hm_bench_sil_kernels; hm_sil_parts returns NULL); alpha_full 8 bytes (written as float2); keep and ref 8 bytes in the
+ *     per-sample mode, i.e. when given together with alpha_full or with mask_shared bit 1 (read as float2) - the pooled-mode
+ *     keep / ref (B,S,S) need 4. */
 size_t hm_sil_workspace_bytes(int B, int V, int F, int S);
 int hm_sil_fwd(const float* verts, const int* faces, int faces_bstride, const float* K, int B, int V, int F, int S,
                float orig_size, float znear, float zfar, const float* keep, const float* ref,
@@ -198,7 +215,8 @@ int hm_sil_reduce(int B, int V, int F, int S, const float* keep_sum, float* loss
  * mode 1: upstream (1) = dL/d loss_out[0]; mode 2: same with upstream[0] > 0 guaranteed by the caller (the forward's
  * sweep planes are reused, one launch less); mode 0: grad_pooled (B,S,S) = dL/d pooled.  adj_off (V+1), adj_items (3F):
  * CSR vertex -> (face*3 + corner).  grad_verts (B,V,3) overwritten, or NULL to skip the vertex gather (the
- * per-corner gradients stay in the workspace: hm_sil_parts / hm_rigid_bwd_sil); grad_ndc (B,V,3) optional. */
+ * per-corner gradients stay in the workspace: hm_sil_parts / hm_rigid_bwd_sil); grad_ndc (B,V,3) optional.
+ * ALIGNMENT: workspace base 16 bytes; grad_pooled 8 bytes in mode 3 (read as float2; 4 in mode 0). */
 int hm_sil_bwd(const float* verts, const float* K, int B, int V, int F, int S, float orig_size, float eps, int mode,
                const float* upstream, const float* grad_pooled, const float* keep_sum, const int* adj_off,
                const int* adj_items, float* grad_verts, float* grad_ndc, void* workspace,
@@ -212,7 +230,8 @@ int hm_depth_bwd(const float* verts, const float* K, int B, int V, int F, int S,
  * one per (frame, pixel row, 64-pixel segment), non-zero wherever some pixel of the segment has a non-zero gradient (as
  * hm_ordinal_depth_bwd_flags writes them; a set byte over an all-zero segment is harmless).  An ordinal depth term is zero
  * wherever render and annotation agree on the order - nearly everywhere -, and faces / frames that touch no flagged segment
- * get their exact zeros without being walked.  Same result as hm_depth_bwd. */
+ * get their exact zeros without being walked.  Same result as hm_depth_bwd.
+ * ALIGNMENT: workspace base 16 bytes; gflags 4 bytes (scanned four bytes at a time). */
 int hm_depth_bwd_sparse(const float* verts, const float* K, int B, int V, int F, int S, float orig_size,
                         const float* grad_pooled_depth, const int* adj_off, const int* adj_items, float* grad_verts,
                         const unsigned char* gflags, void* workspace, hipStream_t stream);
@@ -298,7 +317,8 @@ int hm_sil_read_owned(const void* workspace, int B, int V, int F, int S, void* o
  *   sigma receives none.  alpha = the forward's output for the same arguments; grad_alpha (B,S,S); adj_off (V+1) / adj_items (3F)
  *   as for hm_sil_bwd; grad_verts (B,V,3) is overwritten.
  *   Any S in 1..4096, F >= 1, B >= 1 (else HM_ERR_BAD_ARG, like a NULL pointer: nothing is launched, outputs stay untouched).
- *   workspace: hm_softsil_workspace_bytes bytes (0 for shapes outside that range), no initialisation needed.  Every sum has a
+ *   workspace: hm_softsil_workspace_bytes bytes (0 for shapes outside that range), no initialisation needed; ALIGNMENT: its base
+ *   4 bytes.  Every sum has a
  *   fixed order and no result goes through an atomic: two calls on the same inputs return the same bits. */
 size_t hm_softsil_workspace_bytes(int B, int V, int F, int S);
 int hm_softsil_fwd(const float* verts, const int* faces, const float* K, int B, int V, int F, int S, float orig_size,
@@ -318,7 +338,7 @@ int hm_softsil_bwd(const float* verts, const int* faces, const float* K, int B, 
  *   are the same bits whatever N is and from call to call.
  *   1 <= S <= 4096, 1 <= N <= 65535, no NULL pointer, else HM_ERR_BAD_ARG: nothing is launched, the outputs stay untouched.
  *   workspace: hm_softsil_pose_workspace_bytes(N, S) bytes (0 for shapes outside that range), zero-filled once (self-resetting
- *   tickets).
+ *   tickets).  ALIGNMENT: workspace base 4 bytes; alpha, keep, ref, grad 4 bytes (16 selects the vector path, nothing else).
  * hm_sigma_anneal: sigma[0] <- max(sigma[0] * decay, sigma_min) in float32, one multiply and one max, on the stream: the blur
  *   schedule of a captured loop (sigma is the device float the soft kernels read when they run).  0 < decay <= 1,
  *   0 <= sigma_min < inf, else HM_ERR_BAD_ARG.  A sigma that underflows to 0 renders empty, see above. */
@@ -328,7 +348,8 @@ int hm_softsil_pose_terms(const float* alpha, const float* keep, const float* re
 int hm_sigma_anneal(float* sigma, float decay, float sigma_min, hipStream_t stream);
 
 /* ------------------------------------------------------------------ small losses (value + unit gradient in one launch)
- * workspace for all of them: hm_reduce_workspace_bytes(), zero-filled once. */
+ * workspace for all of them: hm_reduce_workspace_bytes(), zero-filled once; ALIGNMENT: base 4 bytes, here and wherever a reduce
+ * workspace is taken (hm_nn_fwd*, hm_contact_fwd*, hm_ordinal_depth_fwd, the ws_* of hm_pair_terms_fwd_clips, the *_clips forms). */
 size_t hm_reduce_workspace_bytes(void);
 /* reference homan/losses.py:141-164: out2[0] = mean sum_xy (proj - ref/image_size)^2, out2[1] = mean px distance */
 int hm_v2d_fwd(const float* verts, const float* camintr, int hand_nb, const float* ref2d, float image_size, int N,
@@ -361,7 +382,8 @@ int hm_contact_fwd(const float* verts_hand, const float* verts_obj, const int* n
  * neighbours between x (B,N,3) and y (B,M,3), both directions, d2 = (dx*dx + dy*dy) + dz*dz in fp32, ties to the lowest
  * index.  aff_x / aff_y (B,5) optional per-frame affine applied on load: p' = ((p - c) / div) * mul, row (cx,cy,cz,div,mul).
  * x_d2 / x_idx (B,N) and y_d2 / y_idx (B,M) optional per-point outputs.  out4 (B,4) double: mean d2 x->y, mean d2 y->x,
- * mean distance x->y, mean |x_i - y_i| (NaN when N != M).  workspace: hm_cloud_metrics_workspace_bytes(B, N, M) bytes.
+ * mean distance x->y, mean |x_i - y_i| (NaN when N != M).  workspace: hm_cloud_metrics_workspace_bytes(B, N, M) bytes, no
+ * initialisation needed; ALIGNMENT: workspace base 8 bytes (doubles).
  * A frame's values do not depend on the other frames of the call. */
 size_t hm_cloud_metrics_workspace_bytes(int B, int N, int M);
 int hm_cloud_metrics(const float* x, const float* y, int B, int N, int M, const float* aff_x, const float* aff_y, float* x_d2,
@@ -386,7 +408,7 @@ int hm_align_stats(const float* gt_hand, const float* pred_hand, int B, int hand
  * The host arrays are checked first (HM_ERR_BAD_ARG: order, first and last key, gather range, signs) and nothing is enqueued
  * when they fail.  Then they are copied, on `stream`, into the caller's device buffers key_frames_dev (K ints) and gather_dev
  * (M ints; NULL without gather), which the kernel reads: the host arrays are read during the call only (pageable memory), so
- * the call is stream-ordered but not capturable in a hipGraph. */
+ * the call is stream-ordered but not capturable in a hipGraph.  `out` is a typed void pointer: 4 bytes (fp32) or 8 (fp64). */
 int hm_keyframe_interp(const float* key_vals, const int* key_frames, int K, int N, int frame_nb, const int* gather, int M,
                        const float* signs, int out_f64, int* key_frames_dev, int* gather_dev, void* out, hipStream_t stream);
 
@@ -415,7 +437,8 @@ int hm_procrustes_align(const float* pred, const float* gt, int B, int N, int mo
  * t_{steps-1} = val_max.  dist: n values on the device, fp32 (is_f64 == 0) or double; val_max: HOST pointer to one double
  * (> 0, finite), read during the call; counts: `steps` unsigned 64-bit integers on the device.  Exact: the bin guessed by a
  * division is corrected by comparing against t_k itself.  NaN counts nowhere.  2 <= steps <= 1024; n == 0 is HM_OK, all
- * zero.  PCK = counts / n and AUC = trapz(PCK, t) / val_max are the host's to form from the integers. */
+ * zero.  PCK = counts / n and AUC = trapz(PCK, t) / val_max are the host's to form from the integers.  Typed void pointers:
+ * counts 8 bytes (64-bit words, targets of integer atomics), dist 4 bytes (fp32) or 8 (double). */
 int hm_threshold_counts(const void* dist, long n, int is_f64, const double* val_max, int steps, void* counts, hipStream_t stream);
 /* F-scores off the squared fp32 nearest-neighbour distances hm_cloud_metrics writes: x_d2 (B,N) of the prediction, y_d2 (B,M)
  * of the ground truth; thresholds: HOST float[T], 1 <= T <= 8, read during the call.  out (B,T,3) double = {precision, recall,
@@ -441,13 +464,14 @@ int hm_fscore(const float* x_d2, const float* y_d2, int B, int N, int M, const f
  * an empty box (an extent of 0) gives zeros.  The call clears `words` itself.  Two calls return the same bits, a frame does not
  * depend on the others, and a voxel does not depend on the box that asked for it.
  * HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: B, V or F < 1, a NULL pointer, a pitch that is not finite and positive,
- * a negative dimension or extent, nx > 32 * NWX, ny > NY, nz > NZ, an index outside [-2^22, 2^22]. */
+ * a negative dimension or extent, nx > 32 * NWX, ny > NY, nz > NZ, an index outside [-2^22, 2^22].  `words` is a typed void
+ * pointer: 4 bytes. */
 int hm_solid_voxels(const float* verts, const int* faces, int B, int V, int F, float pitch, const int* boxes, int NWX, int NY,
                     int NZ, int* boxes_dev, void* words, hipStream_t stream);
 /* a (a_sets, B, words_per_frame) and b (B, words_per_frame) uint32 on the device -> counts (B,3) unsigned 64-bit integers
  * {popcount(A & b), popcount(A), popcount(b)} per frame with A the OR of the a_sets arrays of a: two hands are voxelised
  * separately and OR-ed, since parity over a merged mesh would cancel where the hands overlap each other.
- * words_per_frame == 0 is HM_OK, all zero. */
+ * words_per_frame == 0 is HM_OK, all zero.  Typed void pointers: a, b 4 bytes; counts 8 bytes. */
 int hm_voxel_overlap(const void* a, int a_sets, const void* b, int B, long words_per_frame, void* counts, hipStream_t stream);
 /* out[b] = |sum_f det(p1 - r, p2 - r, p3 - r)| / 6 with r the frame's vertex 0: differences and determinant in double from the
  * fp32 vertices; thread t of the frame's 256-thread workgroup sums the faces t, t + 256, ... in that order and the 256 sums are
@@ -484,7 +508,8 @@ int hm_mesh_volume(const float* verts, const int* faces, int B, int V, int F, do
  * parity are merged through integer operations only (csrc/surfdist.hip).  workspace: hm_point_mesh_workspace_bytes(B, N, F)
  * bytes (0 for batches large enough that the faces of a frame are not split; NULL is then accepted); the call initialises it
  * on `stream`.  HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: B, N, V or F < 1, a NULL input, all four outputs NULL, a
- * NULL workspace where bytes are needed.  Every index is a 64-bit product of the int sizes: no size is refused for overflow. */
+ * NULL workspace where bytes are needed.  Every index is a 64-bit product of the int sizes: no size is refused for overflow.
+ * ALIGNMENT: workspace base 8 bytes (64-bit words, targets of atomicMin). */
 size_t hm_point_mesh_workspace_bytes(int B, int N, int F);
 int hm_point_mesh_distance(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, float* d2,
                            int* face_idx, int* inside, float* closest, void* workspace, hipStream_t stream);
@@ -528,7 +553,9 @@ int hm_point_mesh_distance(const float* points, const float* verts, const int* f
  * NULL input, required output or workspace, a threshold that is not positive and finite, |log2q| > 100.
  * hm_surface_contact_bwd: the autograd backward, upstream (2) fp32 on the device = (dL/dA, dL/dR):
  *   grad_points[i] = (inside ? upstream[1] : upstream[0]) * unit_points[i]; grad_verts = upstream[0] * unit_verts_attr +
- *   upstream[1] * unit_verts_rep; either output may be NULL (its inputs are then not read). */
+ *   upstream[1] * unit_verts_rep; either output may be NULL (its inputs are then not read).
+ * ALIGNMENT: workspace base 8 bytes (64-bit accumulator words, targets of integer atomics, lie at the base; the search's words
+ * follow at a multiple of 8). */
 size_t hm_surface_contact_workspace_bytes(int B, int N, int V, int F);
 int hm_surface_contact_fwd(const float* points, const float* verts, const int* faces, const float* weights, int B, int N, int V,
                            int F, float contact_thresh, float collision_thresh, int log2q, float* out, float* grad_points,
@@ -545,7 +572,8 @@ int hm_surface_contact_bwd(const float* unit_points, const int* inside, const fl
  * = the mask of each ROI (NULL: ROI r crops mask r; an entry outside [0, N) gives an empty crop); boxes (R,4) fp32
  * x1 y1 x2 y2 in pixels; out (R,S,S) bytes 0 / 1.  Every operation is rounded to fp32 and the samples of an output pixel
  * are summed in one lane, rows then columns: the decision at an exact 0.5 tie is that of a scalar loop in that order.
- * R == 0 is HM_OK and launches nothing; S <= 0 and non-positive N, H, W are HM_ERR_BAD_ARG. */
+ * R == 0 is HM_OK and launches nothing; S <= 0 and non-positive N, H, W are HM_ERR_BAD_ARG.  `masks` (and `target`, `occluders`
+ * below) are typed void pointers: 1 byte (bytes) or 4 (fp32). */
 int hm_mask_crop_resize(const void* masks, int masks_f32, int N, int H, int W, const int* index, const float* boxes, int R,
                         int S, unsigned char* out, hipStream_t stream);
 /* The -1 / 0 / 1 fp32 targets of R ROIs in one launch, pixel for pixel the composition of hm_mask_crop_resize calls.
@@ -571,7 +599,8 @@ int hm_instance_masks(const int* idx_map, int B, int S, int F, const int* face_s
 /* ------------------------------------------------------------------ SDF interpenetration
  * reference homan/lossutils.py:43-64 -> homan/interactions/scenesdf.py:77-148 and the `sdf` package (scenesdf.py:119).
  * Scene = {0: hand (closed faces), 1: object}.  out1[0] = sum of grid_sample(clamp(SDF_k,0), verts_l) over both
- * ordered pairs and all frames; g0 / g1 = d out / d verts0 / d verts1. */
+ * ordered pairs and all frames; g0 / g1 = d out / d verts0 / d verts1.  ALIGNMENT: workspace base 16 bytes (float4 triangle records), in
+ * every hm_collision_* entry. */
 size_t hm_collision_workspace_bytes(int B, int V0, int V1, int F0, int F1);
 int hm_collision_fwd(const float* verts0, const int* faces0, int V0, int F0, const float* verts1, const int* faces1,
                      int V1, int F1, int B, float scale_factor, float* g0, float* g1, float* out1, void* workspace,
@@ -594,7 +623,7 @@ int hm_collision_read_needed(int B, int which, int V0, int V1, int F0, int F1, v
  * reference homan/jointopt.py:138-151,192 (torch.optim.Adam, three groups) and :184-189 (loss_evolution).
  * slots: n_tensors records {float* p, g, m, v; long n; float lr; int pad} (hm_adam_slot_bytes() each);
  * step: TWO device int32 words {completed steps (incremented by the launch), ticket word (zero between launches)};
- * zero_grad != 0 clears g after the update. */
+ * zero_grad != 0 clears g after the update.  `slots` is a typed void pointer: 8 bytes. */
 size_t hm_adam_slot_bytes(void);
 int hm_adam_step(const void* slots, int n_tensors, int* step, float beta1, float beta2, float eps, int zero_grad,
                  int blocks_per_tensor, hipStream_t stream);

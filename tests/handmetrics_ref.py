@@ -3,6 +3,8 @@ tests/test_handmetrics.py and tests/test_handmetrics_gpu.py.  The protocol's own
 these lines - not that script - are what the kernels of csrc/evalalign.hip are pinned to."""
 import numpy as np
 
+FSCORE_BAR = 1e-15          # F-scores are quotients of small integers formed in double: a last bit at most
+
 
 def align(pred, gt, mode=0, anchors=(0, 4)):
     """pred, gt (N,3) -> (aligned (N,3) float64, err (N,) float64, (s, R (3,3), t (3,))) with aligned = s * pred @ R.T + t"""

@@ -11,6 +11,8 @@ import torch
 from tests import softsil_ref
 
 FAR = softsil_ref.FAR
+RULE_FACTOR, VALUE_ABS = softsil_ref.RULE_FACTOR, softsil_ref.IMAGE_ABS          # the same 4 x rule
+IOU_REL = 3e-7                  # the IoU off exact sums: one add and one divide in float32
 
 
 def rot6d_to_matrix(r6):

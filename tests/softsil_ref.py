@@ -8,6 +8,9 @@ from oracle import nmr as o_nmr
 NEAR, FAR, CUT, MIN_AREA2 = o_nmr.DEFAULT_NEAR, o_nmr.DEFAULT_FAR, 16.0, 1e-10
 
 
+RULE_FACTOR, IMAGE_ABS = 4, 1e-6          # the kernel may be this many times as far from float64 as the float32 restatement (+ abs, images)
+
+
 def pixel_centres(S, dtype):
     """(S*S, 2) NDC centres, row-major: pixel (r, c) at x = (2c + 1 - S) / S, y = (S - 1 - 2r) / S"""
     i = torch.arange(S, dtype=dtype)

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 778, 4097, 20000)
 PAIRS = ([(n, m) for n in SIZES[:5] for m in SIZES[:5]]
          + [(4097, 63), (63, 4097), (4097, 4097), (20000, 1), (1, 20000), (20000, 65), (778, 20000), (20000, 4097)])
+ALIGN_RTOL, ALIGN_ATOL = 1e-5, 1e-7          # aligned metrics against the reference golden and the restatement
 
 
 def affine_np(p, aff):
@@ -124,18 +125,18 @@ def test_against_reference_golden():
         t = [torch.from_numpy(a) for a in ins]
         if kind == "point":
             got = pointmetrics.get_point_metrics(*t)
-            _close(got["chamfer_dists"], want["chamfer_dists"], 1e-5, 1e-7, tag)
+            _close(got["chamfer_dists"], want["chamfer_dists"], ALIGN_RTOL, ALIGN_ATOL, tag)
             _close(got["add-s"], want["add-s"], 1e-6, 0, tag)
             _close(got["verts_dists"], want["verts_dists"], 1e-6, 0, tag)
             assert all(type(v) is float for vs in got.values() for v in vs)
         else:
             got = pointmetrics.get_align_metrics(*t)
             for k in ("hand_mean_aligned", "obj_chamfer_aligned"):
-                _close(got[k], want[k], 1e-5, 1e-7, f"{tag} {k}")
+                _close(got[k], want[k], ALIGN_RTOL, ALIGN_ATOL, f"{tag} {k}")
             own = pointmetrics.get_align_metrics(*t, pred_centroid_from_gt=False)
             ref_own = restate_align_metrics(*t, pred_centroid_from_gt=False)
             for k in ("hand_mean_aligned", "obj_chamfer_aligned"):
-                _close(own[k], ref_own[k], 1e-5, 1e-7, f"{tag} own centroid {k}")
+                _close(own[k], ref_own[k], ALIGN_RTOL, ALIGN_ATOL, f"{tag} own centroid {k}")
                 assert len(own[k]) == len(want[k])
 
 

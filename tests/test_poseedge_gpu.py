@@ -15,6 +15,7 @@ from tests import util
 GOLD = os.path.join(util.GOLDEN_DIR, "ref_poseinit_cube_n6_s64.npz")
 FUSED_STEP_KERNEL_NODES = 10         # kernel nodes of one captured step at lw_chamfer = 0, counted on the parent commit
 EDGE_STEP_KERNEL_NODES = 11          # ... of the step with the term: hm_pose_edge_terms for hm_sil_reduce, mode 3's mask pass
+EDGE_REL = 1e-5                     # chamfer sum and gradient samples: of the sum of the magnitudes of their addends
 MAX_LOOP_SIZE = 1024                 # largest mask the loop accepts: the edge sweeps take S <= 512 pixels of 2 x 2 samples
 
 
@@ -194,8 +195,8 @@ def test_edge_terms_against_torch_autograd(size, k):
         print(size, k, where, "chamfer rel err", err_c.max(), "gradient rel err", err_g.max(), "chamfer", cham)
         assert np.array_equal(terms[:, 2], mask.astype(np.float32))
         assert np.array_equal(terms[:, 1], want_iou)
-        assert (np.abs(terms[:, 3] - cham) <= 1e-5 * cham_mag).all()
-        assert (np.abs(grad[:, :size, :size] - g) <= 1e-5 * mag).all()
+        assert (np.abs(terms[:, 3] - cham) <= EDGE_REL * cham_mag).all()
+        assert (np.abs(grad[:, :size, :size] - g) <= EDGE_REL * mag).all()
     assert float(terms[:, 3].max()) > 0
     assert np.array_equal(terms[:, 0], terms[:, 2] + np.float32(lw) * terms[:, 3])            # (float32: rounded like the sum of the dict)
 

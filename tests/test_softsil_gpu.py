@@ -106,8 +106,8 @@ def test_forward_and_backward_match_the_restatement(case):
           f"restatement {gref_diff:.3e} kernel {gerr:.3e}")
     assert gmax > 0 and float(c["g64"][..., 2].abs().max()) > 0           # the z components are part of the check
     assert torch.isfinite(alpha).all() and torch.isfinite(grad).all()
-    assert err <= 4 * ref_diff + 1e-6
-    assert gerr <= 4 * gref_diff
+    assert err <= ref.RULE_FACTOR * ref_diff + ref.IMAGE_ABS
+    assert gerr <= ref.RULE_FACTOR * gref_diff
 
 
 def test_soup_edge_faces():
