@@ -1,14 +1,143 @@
 """FusedStepper: the whole optimisation iteration (reference homan/jointopt.py:158-192 over homan/homan.py:421-508) as a fixed
 sequence of C-ABI kernel launches on two or three HIP streams, captured in hipGraphs - the benchmark path.  One clip, a batch
 of equal-shaped clips (homan_amd.clipbatch), or - through homan_amd.shard - a shard of clips of any shapes."""
-from collections import OrderedDict, defaultdict
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import lib as _lib
-from .homan import HOMan
 from .loopcommon import HmAdam, parameter_groups
+
+# the loss terms and logged metrics, in slot order: (slot of `vals` / name in loss_evolution, key of its weight - None: a metric,
+# logged only -, switch of FusedStepper.on).  A switch is on when one of its weights is positive.
+TERMS = (("loss_pca", "lw_pca", "pca"), ("loss_scale_obj", "lw_scale_obj", "so"), ("loss_scale_hand", "lw_scale_hand", "sh"),
+         ("loss_smooth_obj", "lw_smooth_obj", "smooth"), ("loss_smooth_hand", "lw_smooth_hand", "smooth"),
+         ("loss_collision", "lw_collision", "col"), ("loss_contact", "lw_contact", "con"),
+         ("loss_v2d_hand", "lw_v2d_hand", "v2d"), ("v2d_hand", None, "v2d"), ("loss_sil_obj", "lw_sil_obj", "sil"),
+         ("iou_object", None, "sil"), ("loss_inter", "lw_inter", "inter"), ("handobj_maxdist", None, "inter"),
+         ("loss_depth", "lw_depth", "depth"))
+
+
+@dataclass(frozen=True)
+class LaunchPlan:
+    """every scheduling decision of the fused iteration, taken once by `launch_plan` (which says what each one is for)"""
+    use_aux: bool
+    log_in_adam: bool
+    side_own_vo: bool
+    merge_renders: bool
+    sil_reduce_in_bwd: bool
+    pairs_after_lines: bool
+    mano_bwd_rigid: bool
+    pair_fused: bool
+    fuse: bool
+    nn_fused: bool
+    nn_full_fused: bool
+    ht_fused: bool
+    nn_separate: bool
+    sm_in: bool
+    side_terms: bool
+    graph_iters: int
+    sweep_blocks: int
+    raster_lds_pad: int
+    nn_lds_pad: int
+
+
+def launch_plan(C, h, Vo, on, shared_scale=False, inter_min=False, optimize_object_scale=False):
+    """The LaunchPlan of a fit of C clips with h hands per frame and Vo object vertices; `on`: the ten term switches of
+    FusedStepper.on.  Pure (no device, no library): the one place where a launch is placed, merged, split or hinted, and where
+    what must hold between those decisions is checked (tests/test_fused_plan.py walks every admissible input)."""
+    # third stream for the silhouette reduction + log row: it pays on a clip batch (+1.5 %); at one clip the graph executor
+    # spends two cross-queue hops (~10 us each) on it, and two streams are 5-6 % faster (same-box A/B, cfg2 and cfg3)
+    # (with the depth launches on the side stream the three-stream graph dies at replay in the HIP runtime, like the other
+    #  patterns listed at _loop_streams: two streams)
+    use_aux = C > 1 and not on["depth"]
+    # two streams, no shared scale: the log row of a step is written by the Adam launch itself (one launch less)
+    log_in_adam = not use_aux and not shared_scale
+    # the side stream forms the camera-space object vertices ITSELF (hm_rigid_fwd_clips into a buffer of its own: the face
+    # setup's arithmetic, the same floats) instead of waiting for the face setup's copy: the silhouette chain then has no
+    # successor on another queue between the iteration's fork and its join - the rasteriser follows the face setup without
+    # the few microseconds a node with a cross-queue successor costs its own queue (EXPERIMENTS r6)
+    # (not on the step-2 sets: there the hand-side chain is the longer one, and one more launch on it costs what the
+    #  silhouette chain gains - cfg3 5 457 -> 5 221 it/s with it)
+    # (only with the silhouette term: without it there is no face setup, the side stream's own transform writes `vo` and
+    #  every reader of `vo_b` must find it there)
+    side_own_vo = h == 1 and C == 1 and on["sil"] and not on["depth"] and not on["col"] and not on["con"]
+    # with the ordinal depth term the object's two renders of an iteration - ROI silhouette, full-image depth - are ONE launch
+    # pair (hm_sil_fwd_multi; see _issue_silhouette_chain)
+    merge_renders = h == 1 and on["depth"] and on["sil"]
+    # the silhouette loss / IoU values (log only) come out of the backward's first launch: one launch less on the chain
+    # (two streams only: with the third stream the reduction and the log row stay there, behind the raster's event)
+    sil_reduce_in_bwd = not use_aux
+    # iterations per replay of the second graph (run()): one clip, no collective between the halves of an iteration.  The
+    # turnaround between two replays is ~5 us of a 160 us iteration (same-box A/B: +2-3 % at 4, no more at 8 / 16)
+    graph_iters = 4 if C == 1 else 1
+    # a clip batch: the pair-wise terms of the side stream wait for the END of the line expansion (the backward in two
+    # calls) - that kernel is latency-bound and takes 200 us instead of 150 next to neighbours that hold its wave slots -
+    # and the sweeps run 1024 persistent workgroups instead of 1280 so that the hand's gradient launches find registers
+    # next to them (same-box A/B, 8 clips: step-1 8 650 -> 8 865 it/s, step-2 7 142 -> 7 332; either change alone loses).
+    # (Started next to the raster instead, the search / smoothness / interaction launches cost it more - 362 -> 433 us -
+    #  than they gain next to the line expansion - 230 -> 162 us.)
+    pairs_after_lines = C > 1 and on["sil"]
+    # the hand's rigid backward inside the MANO backward's launch (hm_mano_bwd_rigid_clips): one launch less on the hand-side
+    # chain.  One clip: cfg2 +1.3 %, cfg3 +1.4 %; a clip batch hides that chain under the silhouette chain and loses 1-1.6 %
+    # (round 6: a clip batch too, +0.5 % - the separate hand launch was a 1024-thread workgroup per frame that found no room
+    #  next to the persistent sweeps: 106 us on average, up to 365 us in the 8-clip profile of round 5)
+    #  (a step-2 batch keeps the separate launch: 7 715 against 7 647 it/s)
+    mano_bwd_rigid = C == 1 or not (on["col"] or on["con"])
+    # the pair-wise terms in one launch (csrc/pairterms.hip) at one clip: the hand-side chain is the iteration's critical
+    # path, -6 %; a batch hides that chain under the silhouette chain and the fused launch only adds contention there, +1.6 %
+    pair_fused = C == 1
+    # pair terms that feed nothing to each other go in ONE launch (csrc/pairterms.hip): the interaction term, the
+    # object's smoothness, the metric-only search (no contact term) and the hand-only reductions
+    fuse = pair_fused and on["inter"] and Vo <= 4096 and not inter_min
+    nn_fused = fuse and not on["con"]
+    # with the contact term the FULL search (nearest object vertex of every hand vertex) is the launch's first block
+    # range instead, and the contact launches follow it: one launch less on the hand-side chain of the step-2 sets
+    nn_full_fused = fuse and on["con"]
+    ht_fused = fuse and on["smooth"] and on["v2d"]
+    # ... and otherwise the search is a launch of its own (_issue_pair_terms)
+    nn_separate = (on["con"] or on["inter"]) and not nn_fused and not nn_full_fused
+    # the object's smoothness gradient is formed INSIDE the rigid backward from the camera-space vertices the face setup
+    # wrote (same floats as the unit gradient of the smoothness launch times its weight): on the step-1 sets this chain
+    # then needs nothing from the side stream before the join - one cross-queue edge less on the iteration's tail
+    sm_in = on["smooth"] and on["sil"] and Vo <= 24576
+    side_terms = on["con"] or (on["inter"] and optimize_object_scale) or (on["smooth"] and not sm_in) or not on["sil"]
+    # scheduling hint baked into the captured launches: with the collision / contact terms the hand-side stream is
+    # the longer chain and the persistent edge sweeps should leave it more of the GPU (same results either way;
+    # same-box A/B on cfg3, round 2 before the launch fusions: 1280 -> 4030, 768 -> 4130, 512 -> 4194 it/s; after them,
+    # with the raster ballast below: 512 -> 4408, 768 -> 4552, 1024 -> 4537, 1280 -> 4512)
+    sweep_blocks = 768 if (on["col"] or on["con"]) and C == 1 else 1024 if pairs_after_lines else 1280
+    # same idea for the rasteriser: 8 KB of LDS ballast = 4 workgroups per CU instead of 6 leaves registers for the
+    # hand-side kernels (cfg3 one clip: 4347 -> 4500 it/s; cfg2, where that chain is short: 5820 -> 5500, so not there)
+    raster_lds_pad = 4096 if (on["col"] or on["con"]) and C == 1 else 0
+    # and for the metric-only search of a clip batch: its 1680 small, latency-bound workgroups otherwise take every wave
+    # slot of the CUs next to the line expansion (lines 250 -> 226 us, iteration -4.4 % at 3 search workgroups per CU;
+    # 2 per CU make the search itself the tail)
+    # (34 KB: with the sweep's 30.5 KB workgroups a CU then holds 4 sweeps + 1 search, 2 + 2 or 1 + 3 - the mixes the
+    #  40 KB ballast gave next to the 28.9 KB workgroups of the float sweeps; at 40 KB the search found room only
+    #  next to THREE sweep workgroups and took 297 instead of 137 us, same-box profile)
+    nn_lds_pad = 34816 if C > 1 and not on["con"] else 0
+    # ---- what the launch code relies on between these
+    # the aux block waits for ev_ras, which only the split forward records (_issue_silhouette_chain)
+    assert not (use_aux and (side_own_vo or merge_renders))
+    # the silhouette reduction runs exactly once: in the backward's first launch or in the aux block
+    assert sil_reduce_in_bwd != use_aux
+    # the log row is written exactly once: by Adam, by the aux block, or by the join (_issue_join, _iteration)
+    assert log_in_adam == (not use_aux and not shared_scale)
+    # one search where the contact or the interaction term needs one, none otherwise (_issue_pair_terms)
+    assert nn_fused + nn_full_fused + nn_separate == (1 if on["con"] or on["inter"] else 0)
+    # ev_lines is recorded on the silhouette chain only
+    assert on["sil"] or not pairs_after_lines
+    # `vo_b` has one writer per iteration: the face setup (sil, vo_b is vo), the side copy (sil, side_own_vo) or the side's own
+    # transform into `vo` (no sil: vo_b must be vo)
+    assert on["sil"] or not side_own_vo
+    # the main chain skips the wait for ev_pair only when it reads nothing of the side stream's before the join
+    assert side_terms or (on["sil"] and not on["con"] and not (on["inter"] and optimize_object_scale) and
+                          (sm_in or not on["smooth"]))
+    return LaunchPlan(use_aux, log_in_adam, side_own_vo, merge_renders, sil_reduce_in_bwd, pairs_after_lines, mano_bwd_rigid,
+                      pair_fused, fuse, nn_fused, nn_full_fused, ht_fused, nn_separate, sm_in, side_terms, graph_iters,
+                      sweep_blocks, raster_lds_pad, nn_lds_pad)
 
 
 def _morton_order(verts):
@@ -69,9 +198,7 @@ class FusedStepper:
     (one 4-byte RCCL all-reduce on the compute stream between the two captured halves of the iteration), and every
     replica takes the identical Adam step."""
 
-    SLOTS = ["loss_pca", "loss_scale_obj", "loss_scale_hand", "loss_smooth_obj", "loss_smooth_hand", "loss_collision",
-             "loss_contact", "loss_v2d_hand", "v2d_hand", "loss_sil_obj", "iou_object", "loss_inter",
-             "handobj_maxdist", "loss_depth"]
+    SLOTS = [slot for slot, _, _ in TERMS]
     # the raster's launch order follows the measured cost of its workgroups from iteration to iteration (hm_tune_raster_reorder,
     # captured with the iteration; same-box A/B: raster 57 -> 45 us inside the graph at one clip, 356 -> 298 us at eight; the
     # iteration: clip batches and the step-2 sets +0.3..1 %, one-clip step-1 fits +4 % in the steady state and over iterations
@@ -109,11 +236,12 @@ class FusedStepper:
             raise NotImplementedError("two hands per frame: the fused loop takes one clip at a time (a batch of two-hand "
                                       "clips: one stepper per clip, or mode='graph')")
         lw = self.lw = {k: float(v) for k, v in loss_weights.items()}
-        if lw.get("lw_depth", 0) > 0:
-            if not getattr(m, "ordinal_depth", False):
-                # reference homan.py:506-507 calls lossutils.compute_ordinal_depth_loss() without its arguments
-                raise TypeError("compute_ordinal_depth_loss() missing 3 required positional arguments: "
-                                "'masks', 'silhouettes', and 'depths'")
+        on = self.on = {switch: any(key is not None and lw.get(key, 0.0) > 0 for _, key, sw in TERMS if sw == switch)
+                        for _, _, switch in TERMS}
+        if on["depth"] and not getattr(m, "ordinal_depth", False):
+            # reference homan.py:506-507 calls lossutils.compute_ordinal_depth_loss() without its arguments
+            raise TypeError("compute_ordinal_depth_loss() missing 3 required positional arguments: "
+                            "'masks', 'silhouettes', and 'depths'")
         self.shared_scale, self.group = bool(shared_scale), group
         # collectives=False: the caller (ShardStepper: several steppers of one rank) issues the broadcast / all-reduce of the
         # tied scale itself - every rank must issue the same number of collectives whatever its number of steppers
@@ -125,52 +253,17 @@ class FusedStepper:
         B, Vo, Vh = m.B, m.verts_object_og.shape[1], 778          # B = frames of the whole batch
         C, NS = m.C, len(self.SLOTS) + 1
         self.B, self.C, self.clip_len, self.NS = B, C, m.clip_len, NS
-        # third stream for the silhouette reduction + log row: it pays on a clip batch (+1.5 %); at one clip the graph executor
-        # spends two cross-queue hops (~10 us each) on it, and two streams are 5-6 % faster (same-box A/B, cfg2 and cfg3)
-        # (with the depth launches on the side stream the three-stream graph dies at replay in the HIP runtime, like the other
-        #  patterns listed at _loop_streams: two streams)
-        self.use_aux = C > 1 and not lw.get("lw_depth", 0) > 0
-        # two streams, no shared scale: the log row of a step is written by the Adam launch itself (one launch less)
-        self.log_in_adam = not self.use_aux and not self.shared_scale
-        # the side stream forms the camera-space object vertices ITSELF (hm_rigid_fwd_clips into a buffer of its own: the face
-        # setup's arithmetic, the same floats) instead of waiting for the face setup's copy: the silhouette chain then has no
-        # successor on another queue between the iteration's fork and its join - the rasteriser follows the face setup without
-        # the few microseconds a node with a cross-queue successor costs its own queue (EXPERIMENTS r6)
-        # (not on the step-2 sets: there the hand-side chain is the longer one, and one more launch on it costs what the
-        #  silhouette chain gains - cfg3 5 457 -> 5 221 it/s with it)
-        self.side_own_vo = (self.h == 1 and C == 1 and not lw.get("lw_depth", 0) > 0 and not lw.get("lw_collision", 0) > 0 and
-                            not lw.get("lw_contact", 0) > 0)
-        # with the ordinal depth term the object's two renders of an iteration - ROI silhouette, full-image depth - are ONE launch
-        # pair (hm_sil_fwd_multi; see _issue_silhouette_chain)
-        self.merge_renders = self.h == 1 and lw.get("lw_depth", 0) > 0 and lw.get("lw_sil_obj", 0) > 0
-        # the silhouette loss / IoU values (log only) come out of the backward's first launch: one launch less on the chain
-        # (two streams only: with the third stream the reduction and the log row stay there, behind the raster's event)
-        self.sil_reduce_in_bwd = not self.use_aux
+        self.plan = launch_plan(C, h, Vo, on, self.shared_scale, self.inter_min, m.optimize_object_scale)
         self.Vo, self.Vh, self.P = Vo, Vh, m.mano_pca_pose.shape[1]
         f = lambda *shape: torch.zeros(*shape, device=dev)
         N = self.N = B * h                                        # hand rows (hands interleaved frame-major, homan.py:62-63)
         self.vo, self.vm, self.vh = f(B, Vo, 3), f(N, Vh, 3), f(N, Vh, 3)
         # the side stream's view of the object's vertices (see side_own_vo)
-        self.vo_b = torch.zeros_like(self.vo) if self.side_own_vo else self.vo
+        self.vo_b = torch.zeros_like(self.vo) if self.plan.side_own_vo else self.vo
         self.vals = f(C, NS)                                      # row c: the loss / metric slots of clip c + its total
-        on = lambda k: lw.get(k, 0.0) > 0
-        self.on = dict(pca=on("lw_pca"), so=on("lw_scale_obj"), sh=on("lw_scale_hand"),
-                       smooth=on("lw_smooth_hand") or on("lw_smooth_obj"), col=on("lw_collision"),
-                       con=on("lw_contact"), v2d=on("lw_v2d_hand"), sil=on("lw_sil_obj"), inter=on("lw_inter"),
-                       depth=on("lw_depth"))
-        w = {"loss_pca": lw["lw_pca"] if self.on["pca"] else 0, "loss_scale_obj": lw["lw_scale_obj"] if self.on["so"] else 0,
-             "loss_scale_hand": lw["lw_scale_hand"] if self.on["sh"] else 0,
-             "loss_smooth_obj": lw["lw_smooth_obj"] if self.on["smooth"] else 0,
-             "loss_smooth_hand": lw["lw_smooth_hand"] if self.on["smooth"] else 0,
-             "loss_collision": lw["lw_collision"] if self.on["col"] else 0,
-             "loss_contact": lw["lw_contact"] if self.on["con"] else 0,
-             "loss_v2d_hand": lw["lw_v2d_hand"] if self.on["v2d"] else 0,
-             "loss_sil_obj": lw["lw_sil_obj"] if self.on["sil"] else 0,
-             "loss_inter": lw["lw_inter"] if self.on["inter"] else 0,
-             "loss_depth": lw["lw_depth"] if self.on["depth"] else 0}
-        self.w = w
+        w = self.w = {slot: lw[key] if on[switch] else 0 for slot, key, switch in TERMS if key is not None}
         self.weights = torch.tensor([w.get(k, 0.0) for k in self.SLOTS], device=dev)
-        self.keys = [k for k in self.SLOTS if self._reported(k)]
+        self.keys = [slot for slot, _, switch in TERMS if on[switch]]
         # the object's smoothness VALUE (its gradient is formed inside the rigid backward) rides the pair-terms launch of the side
         # stream as a block range.  Until round 6 the step-2 sets launched it on the silhouette chain instead, behind the sweeps
         # (round 3: cfg3 +5 % while the hand side was by far the longer chain); since the hand side's launches were fused the
@@ -214,7 +307,6 @@ class FusedStepper:
         # bounding spheres, in MESH space, of the groups of 64 vertices in that order, per frame (a clip's frames share one mesh,
         # the clips of a batch need not): centre = mean, radius = farthest vertex.  The search carries them into camera space
         # with the frame's rigid transform instead of reducing the transformed vertices of every group in every workgroup.
-        self.Vo, self.B = Vo, B
         with torch.no_grad():
             # (repeats of a real vertex pad the last group: they change nothing but the mean, and are masked out of it)
             self.obj_spheres = self._group_spheres()                                         # (B, ng, 4)
@@ -291,31 +383,12 @@ class FusedStepper:
                                             for n in (N, B))
         self.mano_state = torch.empty(self.L.hm_mano_state_bytes(N), dtype=torch.uint8, device=dev)
         self.graph = self.graph_b = self.graph_k = None
-        # iterations per replay of the second graph (run()): one clip, no collective between the halves of an iteration.  The
-        # turnaround between two replays is ~5 us of a 160 us iteration (same-box A/B: +2-3 % at 4, no more at 8 / 16)
-        self.graph_iters = 4 if C == 1 else 1
         self.cap_stream, self.side, self.aux, side = _loop_streams(dev)
         self.ev_vo, self.ev_pair, self.ev_sil, self.ev_fwd, self.ev_ras = (torch.cuda.Event() for _ in range(5))
         self.ev_dep, self.ev_dgrad, self.ev_lines = (torch.cuda.Event() for _ in range(3))
         self.reduce_ws_b = ClipReduceWorkspace(dev, C)
         # (the terms of the fused pair-terms launch run side by side: a reduce workspace each)
         self.reduce_ws_c, self.reduce_ws_d, self.reduce_ws_e = (ClipReduceWorkspace(dev, C) for _ in range(3))
-        # a clip batch: the pair-wise terms of the side stream wait for the END of the line expansion (the backward in two
-        # calls) - that kernel is latency-bound and takes 200 us instead of 150 next to neighbours that hold its wave slots -
-        # and the sweeps run 1024 persistent workgroups instead of 1280 so that the hand's gradient launches find registers
-        # next to them (same-box A/B, 8 clips: step-1 8 650 -> 8 865 it/s, step-2 7 142 -> 7 332; either change alone loses).
-        # (Started next to the raster instead, the search / smoothness / interaction launches cost it more - 362 -> 433 us -
-        #  than they gain next to the line expansion - 230 -> 162 us.)
-        self.pairs_after_lines = C > 1 and self.on["sil"]
-        # the hand's rigid backward inside the MANO backward's launch (hm_mano_bwd_rigid_clips): one launch less on the hand-side
-        # chain.  One clip: cfg2 +1.3 %, cfg3 +1.4 %; a clip batch hides that chain under the silhouette chain and loses 1-1.6 %
-        # (round 6: a clip batch too, +0.5 % - the separate hand launch was a 1024-thread workgroup per frame that found no room
-        #  next to the persistent sweeps: 106 us on average, up to 365 us in the 8-clip profile of round 5)
-        #  (a step-2 batch keeps the separate launch: 7 715 against 7 647 it/s)
-        self.mano_bwd_rigid = C == 1 or not (self.on["col"] or self.on["con"])
-        # the pair-wise terms in one launch (csrc/pairterms.hip) at one clip: the hand-side chain is the iteration's critical
-        # path, -6 %; a batch hides that chain under the silhouette chain and the fused launch only adds contention there, +1.6 %
-        self.pair_fused = C == 1
         if self.shared_scale:
             self._sync_shared_scale_start()
         side.wait_stream(torch.cuda.current_stream())
@@ -332,32 +405,16 @@ class FusedStepper:
             # the object's depth render keeps the static order (sorted: +-0 alone, -1 % with the hand's)
             self.dctx[1].calibrate()
         if capture:
-            # scheduling hint baked into the captured launches: with the collision / contact terms the hand-side stream is
-            # the longer chain and the persistent edge sweeps should leave it more of the GPU (same results either way;
-            # same-box A/B on cfg3, round 2 before the launch fusions: 1280 -> 4030, 768 -> 4130, 512 -> 4194 it/s; after them,
-            # with the raster ballast below: 512 -> 4408, 768 -> 4552, 1024 -> 4537, 1280 -> 4512)
-            sb = 768 if (self.on["col"] or self.on["con"]) and C == 1 else 1024 if self.pairs_after_lines else 1280
-            # same idea for the rasteriser: 8 KB of LDS ballast = 4 workgroups per CU instead of 6 leaves registers for the
-            # hand-side kernels (cfg3 one clip: 4347 -> 4500 it/s; cfg2, where that chain is short: 5820 -> 5500, so not there)
-            pad = 4096 if (self.on["col"] or self.on["con"]) and C == 1 else 0
-            # and for the metric-only search of a clip batch: its 1680 small, latency-bound workgroups otherwise take every wave
-            # slot of the CUs next to the line expansion (lines 250 -> 226 us, iteration -4.4 % at 3 search workgroups per CU;
-            # 2 per CU make the search itself the tail)
-            # (34 KB: with the sweep's 30.5 KB workgroups a CU then holds 4 sweeps + 1 search, 2 + 2 or 1 + 3 - the mixes the
-            #  40 KB ballast gave next to the 28.9 KB workgroups of the float sweeps; at 40 KB the search found room only
-            #  next to THREE sweep workgroups and took 297 instead of 137 us, same-box profile)
-            nn_pad = 34816 if C > 1 and not self.on["con"] else 0
             # the hints are per-thread values read when a launch is issued (= captured): set, capture, restore - whatever
             # happens in between (a capture that raises must not leave them changed for the next stepper)
-            tune = _lib.lib()
-            prev = tune.hm_tune_sweep_blocks(sb)
-            prev_pad = tune.hm_tune_raster_lds_pad(pad)
-            prev_reorder = tune.hm_tune_raster_reorder(self.raster_reorder)
-            prev_nn_pad = tune.hm_tune_nn_lds_pad(nn_pad)
+            tune, p, prev = _lib.lib(), self.plan, []
             try:
+                for name, value in (("hm_tune_sweep_blocks", p.sweep_blocks), ("hm_tune_raster_lds_pad", p.raster_lds_pad),
+                                    ("hm_tune_raster_reorder", self.raster_reorder), ("hm_tune_nn_lds_pad", p.nn_lds_pad)):
+                    prev.append((name, getattr(tune, name)(value)))
                 self.graph = _lib.new_graph()
                 with torch.cuda.graph(self.graph, stream=self.cap_stream):
-                    self.forward_backward(log=not self.log_in_adam)
+                    self.forward_backward(log=not p.log_in_adam)
                     if not self.shared_scale:
                         self._capture_step()
                 if self.shared_scale:        # the all-reduce of the scale gradient runs between two captured halves
@@ -365,18 +422,16 @@ class FusedStepper:
                     with torch.cuda.graph(self.graph_b, stream=self.cap_stream):
                         self._spread_shared_scale_grad()
                         self.opt.step(zero_grad=False)
-                elif self.graph_iters > 1:
+                elif p.graph_iters > 1:
                     # K iterations in ONE graph: the boundary between two replays (the executor's own start-up, a few
                     # microseconds of an iteration that lasts 160) is paid once per K iterations; run() replays this graph
                     # for every full K and the one-iteration graph for the rest - the same launches either way
                     self.graph_k = _lib.new_graph()
                     with torch.cuda.graph(self.graph_k, stream=self.cap_stream):
-                        self._capture_iterations(self.graph_iters)
+                        self._capture_iterations(p.graph_iters)
             finally:
-                tune.hm_tune_sweep_blocks(prev)
-                tune.hm_tune_raster_lds_pad(prev_pad)
-                tune.hm_tune_raster_reorder(prev_reorder)
-                tune.hm_tune_nn_lds_pad(prev_nn_pad)
+                for name, value in reversed(prev):
+                    getattr(tune, name)(value)
 
     # ---- other clips into the resident stepper
     def reload(self, clip_inputs):
@@ -470,13 +525,6 @@ class FusedStepper:
         g = self.model.int_scales_object.grad
         g.copy_(self.g_shared.expand_as(g))
 
-    def _reported(self, k):
-        o = self.on
-        return {"loss_pca": o["pca"], "loss_scale_obj": o["so"], "loss_scale_hand": o["sh"], "loss_smooth_obj": o["smooth"],
-                "loss_smooth_hand": o["smooth"], "loss_collision": o["col"], "loss_contact": o["con"],
-                "loss_v2d_hand": o["v2d"], "v2d_hand": o["v2d"], "loss_sil_obj": o["sil"], "iou_object": o["sil"],
-                "loss_inter": o["inter"], "handobj_maxdist": o["inter"], "loss_depth": o["depth"]}[k]
-
     def _slot(self, name):
         """device address of slot `name` of clip 0; clip c is `self.NS` floats further (the kernels' out_stride)"""
         i = self.SLOTS.index(name)
@@ -493,20 +541,18 @@ class FusedStepper:
         is part of the design: the graph executor maps the captured branches onto its queues by it (EXPERIMENTS.md)."""
         if self.h > 1:
             return self._forward_backward_hands(log)
-        it = self._iteration_namespace(log)
-        main = it.main
-        self.side.wait_stream(main)
-        self._issue_silhouette_chain(it)
+        self.side.wait_stream(torch.cuda.current_stream())
+        self._issue_silhouette_chain()
         with torch.cuda.stream(self.side):
-            self._issue_hand_forward(it)
+            self._issue_hand_forward()
             # (issued in this order on purpose - with the depth term too: its renders BEFORE the pair-wise terms put the hand's
             #  raster next to the silhouette raster, cfg2 + depth 4 000 -> 3 790 it/s, EXPERIMENTS r6)
-            self._issue_pair_terms(it)
+            self._issue_pair_terms()
             if self.on["depth"]:
-                self._issue_depth_terms(it)
-            self._issue_hand_backward(it)
-        self._issue_object_backward(it)
-        self._issue_join(it)
+                self._issue_depth_terms()
+            self._issue_hand_backward(log)
+        self._issue_object_backward()
+        self._issue_join(log)
 
     # ---- hooks of the capture (tools/chain_only.py overrides them for its measurement-only launch graphs)
     def _build_optimizers(self, lr):
@@ -519,26 +565,13 @@ class FusedStepper:
     def _capture_iterations(self, K):
         """K iterations of the second graph"""
         for _ in range(K):
-            self.forward_backward(log=not self.log_in_adam)
+            self.forward_backward(log=not self.plan.log_in_adam)
             self._capture_step()
 
-    def _iteration_namespace(self, log=False):
-        """what the per-chain issue builders share (forward_backward)"""
-        from types import SimpleNamespace
-        m, P = self.model, _lib.ptr
-        main = torch.cuda.current_stream()
-        return SimpleNamespace(m=m, L=self.L, P=P, ck=_lib.check, B=self.B, Vo=self.Vo, Vh=self.Vh, c=self.c, on=self.on, w=self.w,
-                               CL=self.clip_len, NS=self.NS, C=self.C, main=main, side=self.side, sa=main.cuda_stream,
-                               sb=self.side.cuda_stream, rws_b=P(self.reduce_ws_b.buf), sctx=m.sil_ctx,
-                               cctx=m.collision_ctx, pca=m.mano_pca_pose, rot=m.mano_rot, betas=m.mano_betas,
-                               mtr=m.mano_trans if m.optimize_mano else None, npca=self.P * self.clip_len,      # PCA entries of one clip
-                               use_aux=self.use_aux, log=log)
-
-    def _aux_block(self, it):
+    def _aux_block(self, log):
         """the silhouette reduction and the log row on the third stream (clip batches)"""
-        (m, L, P, ck, on, CL, NS, C, sctx, use_aux, log) = \
-            (it.m, it.L, it.P, it.ck, it.on, it.CL, it.NS, it.C, it.sctx, it.use_aux, it.log)
-        if not use_aux:
+        m, L, P, ck = self.model, self.L, _lib.ptr, _lib.check
+        if not self.plan.use_aux:
             return
         # the silhouette reduction and the log row run on a third stream, off both chains.  (Only this: HIP stream
         # capture crashes when two captured streams wait for each other's events in both directions, and the hipGraph
@@ -547,18 +580,19 @@ class FusedStepper:
         # behind that chain, +20 us on the iteration.)
         with torch.cuda.stream(self.aux):
             self.aux.wait_event(self.ev_fwd)
-            if on["sil"]:
+            if self.on["sil"]:
                 self.aux.wait_event(self.ev_ras)
-                ck(sctx.reduce(keep_sum=m.keep_sum, loss_out=self._slot("loss_sil_obj"), clip_len=CL, out_stride=NS,
-                               stream=self.aux.cuda_stream), "sil_reduce")
+                ck(m.sil_ctx.reduce(keep_sum=m.keep_sum, loss_out=self._slot("loss_sil_obj"), clip_len=self.clip_len,
+                                    out_stride=self.NS, stream=self.aux.cuda_stream), "sil_reduce")
             if log:
                 ck(L.hm_log_total_clips(P(self.vals), P(self.weights), len(self.SLOTS), P(self.opt.step_t),
-                                        self.max_steps, P(self.log_buf), C, self.aux.cuda_stream), "log")
+                                        self.max_steps, P(self.log_buf), self.C, self.aux.cuda_stream), "log")
 
-    def _issue_silhouette_chain(self, it):
+    def _issue_silhouette_chain(self):
         """A, first half: face setup (+ camera-space vertices), fork point, rasteriser, [object depth render], line expansion + sweeps"""
-        (m, L, ck, on, CL, NS, main, sa, sctx, use_aux) = \
-            (it.m, it.L, it.ck, it.on, it.CL, it.NS, it.main, it.sa, it.sctx, it.use_aux)
+        m, L, ck, on, plan = self.model, self.L, _lib.check, self.on, self.plan
+        CL, NS, sctx, main = self.clip_len, self.NS, m.sil_ctx, torch.cuda.current_stream()
+        sa = main.cuda_stream
         # ---------------- A: silhouettes forward + backward (the critical chain: nothing else rides it; the object's rigid
         # transform is applied inside the face setup, the other losses get the vertices from the side stream)
         if on["sil"]:
@@ -567,7 +601,7 @@ class FusedStepper:
                           rigid_rot6d=m.rotations_object, rigid_trans=m.translations_object, rigid_scale=m.int_scales_object,
                           rigid_abs=1, persistent_outputs=1, clip_len=CL, cam_verts_out=self.vo)
             fwd_args = dict(render, out_stride=NS, stream=sa)
-            if self.merge_renders:
+            if plan.merge_renders:
                 # with the ordinal depth term: the silhouette render and the OBJECT's depth render (the same mesh and pose at the
                 # full-image camera) as ONE face-setup launch and ONE raster launch (hm_sil_fwd_multi: per render the arguments
                 # of the two calls below, the depth render forming its vertices from the pose like the silhouette render does -
@@ -584,7 +618,7 @@ class FusedStepper:
                 self.ev_sil.record(main)
                 ck(L.hm_sil_fwd_multi(arr, 2, 2, sa), "sil_fwd_multi(raster)")
                 self.ev_dep.record(main)
-            elif self.side_own_vo:
+            elif plan.side_own_vo:
                 ck(sctx.forward(**fwd_args), "sil_fwd")      # (no successor on the side stream: see side_own_vo)
             else:
                 # the face setup (which also writes the camera-space vertices self.vo), the fork of the side stream, then the
@@ -592,9 +626,9 @@ class FusedStepper:
                 ck(sctx.forward(phases=1, **fwd_args), "sil_fwd(setup)")
                 self.ev_sil.record(main)
                 ck(sctx.forward(phases=2, **fwd_args), "sil_fwd(raster)")
-                if use_aux:
+                if plan.use_aux:
                     self.ev_ras.record(main)     # the tile partials of the fused loss, for the reduction on the third stream
-            if on["depth"] and not self.merge_renders:
+            if on["depth"] and not plan.merge_renders:
                 # the OBJECT's depth render of the ordinal depth term rides this chain, right behind the silhouette raster (its
                 # vertices are the face setup's): the hand's render runs on the side stream meanwhile - two renders after each
                 # other there made the hand side twice as long as this chain
@@ -602,9 +636,9 @@ class FusedStepper:
                 self.ev_dep.record(main)
             # (no vertex gather; the loss / IoU values come out of its first launch)
             bwd_args = dict(upstream=self.up_sil, keep_sum=m.keep_sum, clip_len=CL,
-                            loss_out=self._slot("loss_sil_obj") if self.sil_reduce_in_bwd else None, out_stride=NS, stream=sa)
+                            loss_out=self._slot("loss_sil_obj") if plan.sil_reduce_in_bwd else None, out_stride=NS, stream=sa)
             mode = 2 if self.lw["lw_sil_obj"] > 0 else 1
-            if self.pairs_after_lines:
+            if plan.pairs_after_lines:
                 # a clip batch: the line expansion - latency-bound, and the kernel of this chain that suffers most from
                 # neighbours holding its wave slots - runs ALONE; the pair-wise terms of the side stream wait for its end
                 ck(sctx.backward(self.vo, self.sil_K, mode, phases=1, **bwd_args), "sil_bwd(lines)")
@@ -613,47 +647,43 @@ class FusedStepper:
             else:
                 ck(sctx.backward(self.vo, self.sil_K, mode, **bwd_args), "sil_bwd")
 
-    def _issue_hand_forward(self, it):
+    def _hand_term_args(self):
+        """the hand-only reductions' share of the arguments of hm_hand_terms_fwd_clips / hm_pair_terms_fwd_clips"""
+        m, P, on = self.model, _lib.ptr, self.on
+        return (P(m.ref_verts2d_hand), float(m.image_size), P(self.U_v2d), self._slot("loss_v2d_hand"), P(self.U_smh),
+                self._slot("loss_smooth_hand"), P(m.mano_pca_pose) if (on["pca"] or on["so"] or on["sh"]) else None,
+                self.P * self.clip_len,                                         # PCA entries of one clip
+                P(m.int_scales_object), P(m.int_scale_object_mean), P(m.int_scales_hand),
+                P(m.int_scale_hand_mean), P(self.U_pca), P(self.U_so), P(self.U_sh), self._slot("loss_pca"))
+
+    def _issue_hand_forward(self):
         """B: object / hand vertices, the hand-only terms, then the waits that place the pair-wise terms next to the silhouette chain"""
-        (m, L, P, ck, B, Vo, Vh, on, CL, NS, C, side, sb, rws_b, pca, rot, betas, mtr, npca) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.on, it.CL, it.NS, it.C, it.side, it.sb, it.rws_b, it.pca, it.rot, it.betas, it.mtr, it.npca)
+        m, L, P, ck, on, plan = self.model, self.L, _lib.ptr, _lib.check, self.on, self.plan
+        B, Vo, Vh, CL, NS, side, sb = self.B, self.Vo, self.Vh, self.clip_len, self.NS, self.side, self.side.cuda_stream
+        rws_b, pca = P(self.reduce_ws_b.buf), m.mano_pca_pose
         if not on["sil"]:    # (with the silhouette term the face setup of hm_sil_fwd has written self.vo already)
             ck(L.hm_rigid_fwd_clips(P(m.verts_object_og), P(m.rotations_object), P(m.translations_object),
                                     P(m.int_scales_object), 1, B, Vo, None, P(self.vo), CL, sb), "rigid_fwd(obj)")
-        elif self.side_own_vo:
+        elif plan.side_own_vo:
             ck(L.hm_rigid_fwd_clips(P(m.verts_object_og), P(m.rotations_object), P(m.translations_object),
                                     P(m.int_scales_object), 1, B, Vo, None, P(self.vo_b), CL, sb), "rigid_fwd(obj, side copy)")
         if m.optimize_mano:
-            ck(L.hm_mano_fwd_clips(self.mctx.ptrs, P(pca), self.P, P(rot), P(betas), P(mtr), B, P(self.vm), None,
-                                   P(m.rotations_hand), P(m.translations_hand), P(m.int_scales_hand), P(self.vh),
-                                   P(self.mano_state), CL, sb),
-               "mano_fwd + rigid(hand)")
+            ck(L.hm_mano_fwd_clips(self.mctx.ptrs, P(pca), self.P, P(m.mano_rot), P(m.mano_betas), P(m.mano_trans), B,
+                                   P(self.vm), None, P(m.rotations_hand), P(m.translations_hand), P(m.int_scales_hand),
+                                   P(self.vh), P(self.mano_state), CL, sb), "mano_fwd + rigid(hand)")
         else:           # the hand mesh is the constant `verts_hand_og` (reference homan.py:357-358): rigid transform only
             ck(L.hm_rigid_fwd_clips(P(m.verts_hand_og), P(m.rotations_hand), P(m.translations_hand),
                                     P(m.int_scales_hand), 0, B, Vh, None, P(self.vh), CL, sb), "rigid_fwd(hand)")
-        pri = on["pca"] or on["so"] or on["sh"]
-        # pair terms that feed nothing to each other go in ONE launch (csrc/pairterms.hip): the interaction term, the
-        # object's smoothness, the metric-only search (no contact term) and the hand-only reductions
-        fuse = self.pair_fused and on["inter"] and Vo <= 4096 and not self.inter_min
-        nn_fused = fuse and not on["con"]
-        # with the contact term the FULL search (nearest object vertex of every hand vertex) is the launch's first block
-        # range instead, and the contact launches follow it: one launch less on the hand-side chain of the step-2 sets
-        nn_full_fused = fuse and on["con"]
-        ht_fused = fuse and on["smooth"] and on["v2d"]
-        ht_args = (P(m.ref_verts2d_hand), float(m.image_size), P(self.U_v2d), self._slot("loss_v2d_hand"), P(self.U_smh),
-                   self._slot("loss_smooth_hand"), P(pca) if pri else None, npca,
-                   P(m.int_scales_object), P(m.int_scale_object_mean), P(m.int_scales_hand),
-                   P(m.int_scale_hand_mean), P(self.U_pca), P(self.U_so), P(self.U_sh), self._slot("loss_pca"))
-        if ht_fused:
-            pass
-        elif on["smooth"] and on["v2d"]:       # the three hand-only reductions in one launch
-            ck(L.hm_hand_terms_fwd_clips(P(self.vh), P(m.camintr), 1, ht_args[0], ht_args[1], B, Vh, *ht_args[2:], rws_b, CL,
-                                         NS, sb), "hand terms")
+        if on["smooth"] and on["v2d"]:       # the three hand-only reductions in one launch
+            if not plan.ht_fused:            # (else they ride the pair-terms launch)
+                ht_args = self._hand_term_args()
+                ck(L.hm_hand_terms_fwd_clips(P(self.vh), P(m.camintr), 1, ht_args[0], ht_args[1], B, Vh, *ht_args[2:], rws_b,
+                                             CL, NS, sb), "hand terms")
         else:
-            if pri:
-                ck(L.hm_priors_fwd_clips(P(pca), npca, P(m.int_scales_object), P(m.int_scale_object_mean),
+            if on["pca"] or on["so"] or on["sh"]:
+                ck(L.hm_priors_fwd_clips(P(pca), self.P * CL, P(m.int_scales_object), P(m.int_scale_object_mean),
                                          P(m.int_scales_hand), P(m.int_scale_hand_mean), P(self.U_pca), P(self.U_so),
-                                         P(self.U_sh), self._slot("loss_pca"), C, NS, sb), "priors")
+                                         P(self.U_sh), self._slot("loss_pca"), self.C, NS, sb), "priors")
             if on["smooth"]:
                 ck(L.hm_smooth_fwd_clips(P(self.vh), B, Vh, 1, P(self.U_smh), self._slot("loss_smooth_hand"), rws_b,
                                          CL, NS, sb), "smooth(hand)")
@@ -661,20 +691,17 @@ class FusedStepper:
                 ck(L.hm_v2d_fwd_clips(P(self.vh), P(m.camintr), 1, P(m.ref_verts2d_hand), float(m.image_size), B, Vh,
                                       P(self.U_v2d), self._slot("loss_v2d_hand"), rws_b, CL, NS, sb), "v2d")
         if on["sil"]:
-            if not self.side_own_vo:
+            if not plan.side_own_vo:
                 side.wait_event(self.ev_sil)     # self.vo: camera-space object vertices from the calling stream
-            if self.pairs_after_lines:
+            if plan.pairs_after_lines:
                 side.wait_event(self.ev_lines)   # (scheduling only, see the silhouette chain above)
-        it.fuse = fuse
-        it.ht_args = ht_args
-        it.ht_fused = ht_fused
-        it.nn_full_fused = nn_full_fused
-        it.nn_fused = nn_fused
 
-    def _issue_pair_terms(self, it):
+    def _issue_pair_terms(self):
         """B: collision, nearest-vertex search, contact, interaction (centroid or min) - on the side stream"""
-        (m, L, P, ck, B, Vo, Vh, c, on, w, CL, NS, side, sb, rws_b, cctx, fuse, ht_args, ht_fused, nn_full_fused, nn_fused) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.c, it.on, it.w, it.CL, it.NS, it.side, it.sb, it.rws_b, it.cctx, it.fuse, it.ht_args, it.ht_fused, it.nn_full_fused, it.nn_fused)
+        m, L, P, ck, c, on, w, plan = self.model, self.L, _lib.ptr, _lib.check, self.c, self.on, self.w, self.plan
+        B, Vo, Vh, CL, NS, side, sb = self.B, self.Vo, self.Vh, self.clip_len, self.NS, self.side, self.side.cuda_stream
+        rws_b, cctx = P(self.reduce_ws_b.buf), m.collision_ctx
+        fuse, nn_fused, nn_full_fused = plan.fuse, plan.nn_fused, plan.nn_full_fused
         if on["col"]:
             # (one clip, step-2 sets: the collision chain alone here and the rest of the hand side on the third stream, which
             #  then joins the calling stream - the HIP graph runtime crashes at replay when a forked stream rejoins the SIDE
@@ -686,7 +713,7 @@ class FusedStepper:
             ck(L.hm_smooth_fwd_clips(P(self.vo_b), B, Vo, 1, P(self.U_smo), self._slot("loss_smooth_obj"), rws_b, CL, NS,
                                      sb), "smooth(obj)")
         def search_and_contact():
-            if (on["con"] or on["inter"]) and not nn_fused and not nn_full_fused:
+            if plan.nn_separate:
                 # (without the contact term only the logged distance is needed: metric-only search - its group table
                 #  covers 4096 object vertices, larger meshes take the full search for the same number)
                 full = on["con"] or Vo > 4096 or self.inter_min      # ('min' names the closest PAIR: indices needed)
@@ -712,8 +739,8 @@ class FusedStepper:
                                          self._slot("loss_inter"), P(self.reduce_ws_c.buf),
                                          P(self.U_smo) if on["smooth"] else None,
                                          self._slot("loss_smooth_obj") if on["smooth"] else None, P(self.reduce_ws_d.buf),
-                                         *(ht_args if ht_fused else (None, 0.0, None, None, None, None, None, 0, None, None,
-                                                                     None, None, None, None, None, None)),
+                                         *(self._hand_term_args() if plan.ht_fused else
+                                           (None, 0.0, None, None, None, None, None, 0, None, None, None, None, None, None, None, None)),
                                          P(self.reduce_ws_e.buf), P(self.obj_spheres), P(m.rotations_object),
                                          P(m.translations_object), P(m.int_scales_object), P(self.hand_order),
                                          P(self.nn_idx) if nn_full_fused else None, P(self.nn_d2) if nn_full_fused else None,
@@ -746,10 +773,10 @@ class FusedStepper:
         elif on["inter"] and m.optimize_object_scale:      # the object side of the term reaches the (free) scale: per-vertex form
             ck(L.hm_inter_bwd(P(self.rec), P(self.up_inter), B, Vh, Vo, None, P(self.G_int_o), sb), "inter_bwd")
 
-    def _issue_depth_terms(self, it):
+    def _issue_depth_terms(self):
         """B: ordinal depth term - hand render, pair term per clip, the two depth-map backward passes"""
-        (m, L, P, ck, B, Vo, Vh, on, CL, NS, C, side, sb) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.Vh, it.on, it.CL, it.NS, it.C, it.side, it.sb)
+        m, L, P, ck, on = self.model, self.L, _lib.ptr, _lib.check, self.on
+        B, Vo, Vh, CL, NS, side, sb = self.B, self.Vo, self.Vh, self.clip_len, self.NS, self.side, self.side.cuda_stream
         if on["depth"]:
             ctx_o, ctx_h, m_o, m_h = self.dctx
             Sd, K = ctx_o.S, P(m.camintr)
@@ -759,7 +786,7 @@ class FusedStepper:
             else:
                 self._depth_render(self.vo, ctx_o, self.d_sil_o, self.d_dep_o, sb)
             rw_bytes = L.hm_reduce_workspace_bytes()
-            for ci in range(C):           # per clip: the term normalises over the clip's own pairs and mask counts
+            for ci in range(self.C):      # per clip: the term normalises over the clip's own pairs and mask counts
                 fr = slice(ci * CL, (ci + 1) * CL)
                 args = (P(self.d_dep_o[fr]), P(self.d_dep_h[fr]), P(self.d_sil_o[fr]), P(self.d_sil_h[fr]), P(m_o[fr]),
                         P(m_h[fr]), CL, Sd)
@@ -784,12 +811,13 @@ class FusedStepper:
                                          P(self.d_flags[li]) if self.d_flags is not None else None, P(ctx.workspace), sb),
                    "depth bwd")
 
-    def _issue_hand_backward(self, it):
+    def _issue_hand_backward(self, log=False):
         """B: forward-done / pair-done events, the hand's rigid + MANO backward"""
-        (m, L, P, ck, B, Vh, on, w, CL, pca, rot, betas, mtr, side, sb) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vh, it.on, it.w, it.CL, it.pca, it.rot, it.betas, it.mtr, it.side, it.sb)
+        m, L, P, ck, on, w = self.model, self.L, _lib.ptr, _lib.check, self.on, self.w
+        B, Vh, CL, side, sb = self.B, self.Vh, self.clip_len, self.side, self.side.cuda_stream
+        pca, rot, betas, mtr = m.mano_pca_pose, m.mano_rot, m.mano_betas, m.mano_trans if m.optimize_mano else None
         self.ev_fwd.record(side)          # every forward loss value of this stream exists now
-        self._aux_block(it)
+        self._aux_block(log)
         self.ev_pair.record(side)        # object-side terms of the pair-wise losses are ready
         # hand (full path: MANO + rigid): smooth + v2d + collision + contact, summed with their weights inside the rigid
         # backward; the interaction term reaches the rigid pose only, as one vector per frame (rec[:, 2:5] / Vh)
@@ -800,7 +828,7 @@ class FusedStepper:
                                  (self.G_dep_h if on["depth"] else None, 1.0)])       # (already times its weight)
         g_rig = P(self.G_min_h) if (on["inter"] and self.inter_min) else None
         g_frm = (self.rec.data_ptr() + 8) if (on["inter"] and not self.inter_min) else None
-        if m.optimize_mano and self.mano_bwd_rigid:
+        if m.optimize_mano and self.plan.mano_bwd_rigid:
             # the hand's rigid backward inside the MANO backward's launch: one launch less on this chain
             ck(L.hm_mano_bwd_rigid_clips(self.mctx.ptrs, P(pca), self.P, P(rot), P(betas), B,
                                          P(self.U_pca) if on["pca"] else None, w["loss_pca"], P(pca.grad), P(rot.grad),
@@ -819,10 +847,11 @@ class FusedStepper:
                                  P(betas.grad), P(mtr.grad), P(self.mano_state), P(self.mctx.workspace(B)), sb),
                    "mano_bwd")
 
-    def _issue_object_backward(self, it):
+    def _issue_object_backward(self):
         """A, second half: [object depth backward], the object's rigid backward with the silhouette gather"""
-        (m, L, P, ck, B, Vo, on, w, CL, main, sa, sctx) = \
-            (it.m, it.L, it.P, it.ck, it.B, it.Vo, it.on, it.w, it.CL, it.main, it.sa, it.sctx)
+        m, L, P, ck, on, w = self.model, self.L, _lib.ptr, _lib.check, self.on, self.w
+        B, Vo, CL, sctx, main = self.B, self.Vo, self.clip_len, m.sil_ctx, torch.cuda.current_stream()
+        sa, sm_in, sc_obj = main.cuda_stream, self.plan.sm_in, m.optimize_object_scale
         # ---------------- A: object backward: silhouette gradient + smooth + contact [+ interaction with a free scale],
         # summed with their weights inside the rigid backward
         if on["depth"] and on["sil"]:
@@ -832,13 +861,7 @@ class FusedStepper:
                                      P(ctx_o.adj_items), P(self.G_dep_o),
                                      P(self.d_flags[0]) if self.d_flags is not None else None, P(ctx_o.workspace), sa),
                "depth bwd(obj)")
-        sc_obj = m.optimize_object_scale
-        # the object's smoothness gradient is formed INSIDE the rigid backward from the camera-space vertices the face setup
-        # wrote (same floats as the unit gradient of the smoothness launch times its weight): on the step-1 sets this chain
-        # then needs nothing from the side stream before the join - one cross-queue edge less on the iteration's tail
-        sm_in = on["smooth"] and on["sil"] and Vo <= 24576
-        side_terms = on["con"] or (on["inter"] and sc_obj) or (on["smooth"] and not sm_in) or not on["sil"]
-        if side_terms:
+        if self.plan.side_terms:      # (else this chain needs nothing from the side stream before the join: see sm_in)
             main.wait_event(self.ev_pair)
         tp, tw, tn = _lib.terms([(self.U_smo if (on["smooth"] and not sm_in) else None, w["loss_smooth_obj"]),
                                  (self.U_cono if on["con"] else None, w["loss_contact"]),
@@ -856,21 +879,20 @@ class FusedStepper:
             ck(L.hm_rigid_bwd_clips(P(m.verts_object_og), P(m.rotations_object), P(m.int_scales_object), 1, tp, tw, tn, None,
                                     None, 0, 0.0, B, Vo, None, P(m.rotations_object.grad), P(m.translations_object.grad),
                                     P(self.g_so_part) if sc_obj else None, P(self.rigid_ws_o), CL, sa), "rigid_bwd(obj)")
-        it.sc_obj = sc_obj
 
-    def _issue_join(self, it):
+    def _issue_join(self, log):
         """tail: join, log row (two streams), scale gradients"""
-        (m, L, P, ck, on, w, CL, C, main, side, sa, use_aux, log, sc_obj) = \
-            (it.m, it.L, it.P, it.ck, it.on, it.w, it.CL, it.C, it.main, it.side, it.sa, it.use_aux, it.log, it.sc_obj)
-        main.wait_stream(side)               # join
-        if use_aux:
+        m, L, P, ck, C, main = self.model, self.L, _lib.ptr, _lib.check, self.C, torch.cuda.current_stream()
+        sa = main.cuda_stream
+        main.wait_stream(self.side)          # join
+        if self.plan.use_aux:
             main.wait_stream(self.aux)
         elif log:
             ck(L.hm_log_total_clips(P(self.vals), P(self.weights), len(self.SLOTS), P(self.opt.step_t),
                                     self.max_steps, P(self.log_buf), C, sa), "log")
-        if sc_obj:          # per clip: sum of the frames' d loss / d scale + the scale prior's term
-            ck(L.hm_sum_small_clips(P(self.g_so_part), CL, 1.0, P(self.U_so) if on["so"] else None, w["loss_scale_obj"],
-                                    P(m.int_scales_object.grad), C, sa), "scale grad")
+        if m.optimize_object_scale:          # per clip: sum of the frames' d loss / d scale + the scale prior's term
+            ck(L.hm_sum_small_clips(P(self.g_so_part), self.clip_len, 1.0, P(self.U_so) if self.on["so"] else None,
+                                    self.w["loss_scale_obj"], P(m.int_scales_object.grad), C, sa), "scale grad")
             if self.shared_scale:
                 # ONE scalar tied across the clips: its gradient is the sum of the replicas' gradients - local clips
                 # here, ranks in _reduce_shared_scale_grad
@@ -903,7 +925,7 @@ class FusedStepper:
                                stream=stream_id), "depth render")
 
     def _adam_log(self):
-        if not self.log_in_adam:
+        if not self.plan.log_in_adam:
             return None
         return (self.vals, self.weights, len(self.SLOTS), self.max_steps, self.log_buf, self.C)
 
@@ -914,7 +936,7 @@ class FusedStepper:
                 self._reduce_shared_scale_grad()
                 self.graph_b.replay()
         else:
-            self.forward_backward(log=not self.log_in_adam)
+            self.forward_backward(log=not self.plan.log_in_adam)
             if self.shared_scale:
                 self._reduce_shared_scale_grad()
                 self._spread_shared_scale_grad()
@@ -922,9 +944,9 @@ class FusedStepper:
 
     def run(self, steps):
         if self.graph_k is not None:
-            while steps >= self.graph_iters:
+            while steps >= self.plan.graph_iters:
                 self.graph_k.replay()
-                steps -= self.graph_iters
+                steps -= self.plan.graph_iters
         for _ in range(steps):
             self._iteration()
 

@@ -15,11 +15,10 @@ def forward_backward_hands(self, log=False):
     (h1|obj), logged distance = largest per-frame distance to the NEAREST hand.  Same kernels and values as
     HOMan.forward + autograd; not tuned like the one-hand sequence (no fused pair-term launch)."""
     m, L, P, ck = self.model, self.L, _lib.ptr, _lib.check
-    B, N, h, Vo, Vh, c, on, w = self.B, self.N, self.h, self.Vo, self.Vh, self.c, self.on, self.w
-    NS = self.NS
+    B, N, h, Vo, Vh, c, on, w, NS = self.B, self.N, self.h, self.Vo, self.Vh, self.c, self.on, self.w, self.NS
     main, side = torch.cuda.current_stream(), self.side
     sa, sb = main.cuda_stream, side.cuda_stream
-    rws_a, rws_b = P(m.reduce_ws.buf), P(self.reduce_ws_b.buf)
+    rws_b = P(self.reduce_ws_b.buf)
     sctx, cctx = m.sil_ctx, m.collision_ctx
     pca, rot, betas = m.mano_pca_pose, m.mano_rot, m.mano_betas
     mtr = m.mano_trans if m.optimize_mano else None

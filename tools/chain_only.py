@@ -4,6 +4,7 @@ chain ALONE on one queue (no side stream at all, the hand does not move - a floo
 between them inside the four-iteration graph (not a fit either).  Same process, same box, steppers built one after the other.
 usage (GPU box): python tools/chain_only.py [cfg2 cfg1 b1]"""
 import copy
+import dataclasses
 import json
 import os
 import sys
@@ -32,12 +33,11 @@ class ObjectChainOnly(FusedStepper):
 
     def _build_optimizers(self, lr):
         self.opt = HmAdam(_split_groups(self.model, lr, True))
-        self.side_own_vo = True
+        self.plan = dataclasses.replace(self.plan, side_own_vo=True)
 
     def forward_backward(self, log=False):
-        it = self._iteration_namespace(log)
-        self._issue_silhouette_chain(it)
-        self._issue_object_backward(it)
+        self._issue_silhouette_chain()
+        self._issue_object_backward()
 
 
 class NoEdges(FusedStepper):
@@ -48,7 +48,7 @@ class NoEdges(FusedStepper):
     def _build_optimizers(self, lr):
         self.opt = HmAdam(_split_groups(self.model, lr, True))
         self.opt_hand = HmAdam(_split_groups(self.model, lr, False))
-        self.side_own_vo = True
+        self.plan = dataclasses.replace(self.plan, side_own_vo=True)
         self.vo_b = torch.zeros_like(self.vo)
 
     def _capture_step(self):
@@ -56,19 +56,18 @@ class NoEdges(FusedStepper):
         self.opt_hand.step(zero_grad=False)
 
     def _capture_iterations(self, K):
-        it = self._iteration_namespace(False)
-        it.use_aux = False
-        main = it.main
+        self.plan = dataclasses.replace(self.plan, use_aux=False)
+        main = torch.cuda.current_stream()
         self.side.wait_stream(main)
         for _ in range(K):
-            self._issue_silhouette_chain(it)
-            self._issue_object_backward(it)
+            self._issue_silhouette_chain()
+            self._issue_object_backward()
             self.opt.step(zero_grad=False)
         with torch.cuda.stream(self.side):
             for _ in range(K):
-                self._issue_hand_forward(it)
-                self._issue_pair_terms(it)
-                self._issue_hand_backward(it)
+                self._issue_hand_forward()
+                self._issue_pair_terms()
+                self._issue_hand_backward()
                 self.opt_hand.step(zero_grad=False, log=self._adam_log())
         main.wait_stream(self.side)
 
