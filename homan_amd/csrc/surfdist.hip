@@ -19,12 +19,8 @@
 // the batch.  No floating-point atomics.
 #include "hm_common.h"
 #include "inside_test.h"     // orient2, ray_x_crosses
-#include "surfdist_walk.h"   // SdFace, sd_load_face, sd_closest: the per-face walk, shared with csrc/surfcontact.hip
+#include "surfdist_walk.h"   // SdFace, sd_load_face, sd_closest: the per-face walk, shared with csrc/surfcontact.hip; SD_*, sd_splits
 
-#define SD_THREADS 256
-#define SD_CHUNK 256                     // faces staged per pass: one record per thread (ops.SURFDIST_CHUNK mirrors it)
-#define SD_MAX_GRID_Z 65535
-#define SD_TARGET_BLOCKS 1024            // four workgroups on each of the 256 CUs before the faces stop being split
 #define SD_EMPTY 0x7f800000ffffffffull   // (bits(+inf) << 32) | (unsigned)-1: no face yet
 
 // the outputs of point `at` (= b * N + i) from its merged values; face < 0: no face counted
@@ -118,18 +114,6 @@ __global__ __launch_bounds__(SD_THREADS) void k_point_mesh_finish(const float* _
         sd_write(points, verts + b * V * 3, faces, V, t, __uint_as_float((unsigned int)(m >> 32)), (int)(unsigned int)m,
                  (int)(ws_par[t] & 1u), d2, face_idx, inside, closest);
     }
-}
-
-// how many workgroups share the faces of one frame, and how many chunks each takes
-static inline int sd_splits(int B, int N, int F, int* chunks_per_split)
-{
-    const long chunks = ((long)F + SD_CHUNK - 1) / SD_CHUNK;
-    const long blocks = (long)B * (((long)N + SD_THREADS - 1) / SD_THREADS);
-    long want = (SD_TARGET_BLOCKS + blocks - 1) / blocks;
-    want = want < 1 ? 1 : (want > chunks ? chunks : want);
-    const long per = (chunks + want - 1) / want;
-    *chunks_per_split = (int)per;
-    return (int)((chunks + per - 1) / per);
 }
 
 extern "C" {

@@ -6,6 +6,12 @@
 #pragma once
 #include "hm_common.h"
 
+// launch geometry of the kernels that walk every (point, face) pair: csrc/surfdist.hip and csrc/winding.hip
+#define SD_THREADS 256
+#define SD_CHUNK 256                     // faces staged per pass: one record per thread (ops.SURFDIST_CHUNK mirrors it)
+#define SD_MAX_GRID_Z 65535
+#define SD_TARGET_BLOCKS 1024            // four workgroups on each of the 256 CUs before the faces stop being split
+
 #define SD_SKIPPED 0
 #define SD_TRIANGLE 1
 #define SD_SEGMENTS 2
@@ -129,4 +135,16 @@ __device__ __forceinline__ float sd_closest_w(const float* p, const SdFace& r, f
 __device__ __forceinline__ float sd_closest(const float* p, const SdFace& r, float* q)
 {
     return sd_closest_w<false>(p, r, q, nullptr, nullptr);
+}
+
+// how many workgroups share the faces of one frame, and how many chunks each takes
+static inline int sd_splits(int B, int N, int F, int* chunks_per_split)
+{
+    const long chunks = ((long)F + SD_CHUNK - 1) / SD_CHUNK;
+    const long blocks = (long)B * (((long)N + SD_THREADS - 1) / SD_THREADS);
+    long want = (SD_TARGET_BLOCKS + blocks - 1) / blocks;
+    want = want < 1 ? 1 : (want > chunks ? chunks : want);
+    const long per = (chunks + want - 1) / want;
+    *chunks_per_split = (int)per;
+    return (int)((chunks + per - 1) / per);
 }

@@ -27,7 +27,7 @@ from collections import defaultdict
 import numpy as np
 import torch
 
-from . import constants, handmetrics, lib, ops, pointmetrics
+from . import constants, handmetrics, lib, meshutils, ops, pointmetrics
 
 CAMEXTR_SIGNS = (1.0, -1.0, -1.0)                # diagonal of evalho3drecons.py:101
 UNORDER_IDXS = (0, 5, 6, 7, 10, 11, 12, 17, 18, 19, 13, 14, 15, 1, 2, 3, 4, 8, 12, 16, 20)       # ours -> HO-3D (:105-107)
@@ -211,12 +211,21 @@ def evaluate_sequence_plausibility(seq_res, frame_nb, obj_faces, mano_faces_clos
 
 
 def evaluate_sequence_surface(seq_res, frame_nb, obj_faces, mano_faces_closed, chunk=512, contact_thresh=0.005):
-    """Surface-distance plausibility of every interpolated frame of one sequence (`pointmetrics.get_surface_metrics`); no ground
-    truth is needed.  seq_res, obj_faces, mano_faces_closed and chunk as `evaluate_sequence_plausibility` (the frames are
+    """`evaluate_sequence_surface_signed` with the ray-parity sign, which needs closed meshes: see there."""
+    return evaluate_sequence_surface_signed(seq_res, frame_nb, obj_faces, mano_faces_closed, chunk, contact_thresh, "parity")
+
+
+def evaluate_sequence_surface_signed(seq_res, frame_nb, obj_faces, mano_faces_closed, chunk=512, contact_thresh=0.005,
+                                     sign="parity"):
+    """Surface-distance plausibility of every interpolated frame of one sequence (`pointmetrics.get_surface_metrics_signed`,
+    which `sign` is passed to: "parity", "winding" for meshes that are not closed, or "auto"); no ground truth is needed.
+    seq_res, obj_faces, mano_faces_closed and chunk as `evaluate_sequence_plausibility` (the frames are
     interpolated and flipped the same way) -> per-frame float64 arrays "pen_depth" (hand into object, to the object's surface),
     "pen_depth_obj" (object vertices inside the hand), "min_dist", "contact_share" (hand vertices within `contact_thresh` of
     the surface or inside it) and "has_contact" (0 / 1), and their means over the frames under the same names with "_mean".
     A frame's values do not depend on the chunk size."""
+    if sign not in meshutils.SIGN_MODES:
+        raise ValueError(f"sign {sign!r} not in [parity|winding|auto]")
     if chunk < 1:
         raise ValueError(f"chunk must be positive, got {chunk}")
     if not (np.isfinite(float(contact_thresh)) and float(contact_thresh) >= 0):
@@ -227,8 +236,8 @@ def evaluate_sequence_surface(seq_res, frame_nb, obj_faces, mano_faces_closed, c
     keys = ("pen_depth", "pen_depth_obj", "min_dist", "contact_share", "has_contact")
     lists = {key: [] for key in keys}
     for f0 in range(0, frame_nb, chunk):
-        part = pointmetrics.get_surface_metrics(verts[f0:f0 + chunk], obj[f0:f0 + chunk], hand_faces, object_faces,
-                                                contact_thresh=contact_thresh)
+        part = pointmetrics.get_surface_metrics_signed(verts[f0:f0 + chunk], obj[f0:f0 + chunk], hand_faces, object_faces,
+                                                       contact_thresh=contact_thresh, sign=sign)
         for key in keys:
             lists[key] += part[key]
     res = {key: np.asarray(lists[key], np.float64) for key in keys}

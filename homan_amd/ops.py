@@ -1169,13 +1169,8 @@ def voxel_overlap(a, b):
 SURFDIST_CHUNK = 256             # faces staged through LDS per pass (SD_CHUNK of csrc/surfdist.hip)
 
 
-def point_mesh_distance(points, verts, faces, closest=False):
-    """Exact distance of points (B,N,3) to the triangle meshes verts (B,V,3), faces (F,3) - one topology for all frames - and
-    the inside-outside sign (no grad; csrc/surfdist.hip, the rules in include/homan_amd.h) -> {"d2" (B,N) fp32 squared
-    distance to the nearest face, "face" (B,N) int32 the lowest face that attains it, "inside" (B,N) int32 0 / 1: odd number of
-    faces crossed by the +x ray (meaningful for a closed mesh)} and, with closest, {"closest" (B,N,3) fp32}.  A face that
-    names a vertex outside [0, V) or has a non-finite coordinate is skipped; a non-finite point gets (+inf, -1, 0, 0).  The
-    inputs are moved to the GPU as contiguous fp32 / int32; there is no CPU path."""
+def _point_mesh_inputs(points, verts, faces, who):
+    """the argument checks shared by the point-against-mesh ops -> (device, points, verts, faces) as contiguous fp32 / int32"""
     for name, t in (("points", points), ("verts", verts)):
         if not isinstance(t, torch.Tensor) or not t.is_floating_point():
             raise ValueError(f"{name}: expected a float tensor, got {getattr(t, 'dtype', type(t))}")
@@ -1187,11 +1182,22 @@ def point_mesh_distance(points, verts, faces, closest=False):
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
         raise ValueError(f"faces: expected a non-empty integer (F, 3) array, got {faces.dtype} {tuple(faces.shape)}")
     if not torch.cuda.is_available():
-        raise _lib.HomanAmdError("homan_amd.ops.point_mesh_distance needs the GPU (there is no CPU fallback)")
+        raise _lib.HomanAmdError(f"homan_amd.ops.{who} needs the GPU (there is no CPU fallback)")
     dev = next((t.device for t in (points, verts) if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
     points = points.detach().to(device=dev, dtype=torch.float32).contiguous()
     verts = verts.detach().to(device=dev, dtype=torch.float32).contiguous()
-    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
+    return dev, points, verts, faces.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def point_mesh_distance(points, verts, faces, closest=False):
+    """Exact distance of points (B,N,3) to the triangle meshes verts (B,V,3), faces (F,3) - one topology for all frames - and
+    the inside-outside sign (no grad; csrc/surfdist.hip, the rules in include/homan_amd.h) -> {"d2" (B,N) fp32 squared
+    distance to the nearest face, "face" (B,N) int32 the lowest face that attains it, "inside" (B,N) int32 0 / 1: odd number of
+    faces crossed by the +x ray (meaningful for a closed mesh)} and, with closest, {"closest" (B,N,3) fp32}.  A face that
+    names a vertex outside [0, V) or has a non-finite coordinate is skipped; a non-finite point gets (+inf, -1, 0, 0).  The
+    inputs are moved to the GPU as contiguous fp32 / int32; there is no CPU path.  `point_mesh_distance_signed` is this op with
+    a choice of the sign's rule."""
+    dev, points, verts, faces = _point_mesh_inputs(points, verts, faces, "point_mesh_distance")
     B, N, V, F = points.shape[0], points.shape[1], verts.shape[1], faces.shape[0]
     with torch.cuda.device(dev):
         out = {"d2": torch.empty(B, N, device=dev), "face": torch.empty(B, N, dtype=torch.int32, device=dev),
@@ -1204,6 +1210,64 @@ def point_mesh_distance(points, verts, faces, closest=False):
                                                      _lib.ptr(out["d2"]), _lib.ptr(out["face"]), _lib.ptr(out["inside"]),
                                                      _lib.ptr(out.get("closest")), _lib.ptr(ws), _lib.stream()),
                    "hm_point_mesh_distance")
+    return out
+
+
+WINDING_LOG2Q_MIN = -47          # WN_LOG2Q_MIN of csrc/winding.hip
+
+
+def winding_log2q(F):
+    """The grid 2^L of the exact sum of hm_point_mesh_winding (include/homan_amd.h): L = max(-44, ceil(log2(F)) - 59).  Every
+    solid angle is below 8 in magnitude, so F addends stay below 2^62 quanta of a signed 64-bit count."""
+    if int(F) < 1:
+        raise ValueError(f"winding_log2q: F {F}")
+    return max(-44, (int(F) - 1).bit_length() - 59)
+
+
+def _winding_run(points, verts, faces, log2q):
+    """one hm_point_mesh_winding -> (count (B,N) int64, inside (B,N) int32, log2q), new tensors"""
+    L = None if log2q is None else int(log2q)
+    dev, points, verts, faces = _point_mesh_inputs(points, verts, faces, "point_mesh_winding")
+    B, N, V, F = points.shape[0], points.shape[1], verts.shape[1], faces.shape[0]
+    L = winding_log2q(F) if L is None else L
+    lowest = max(WINDING_LOG2Q_MIN, (F - 1).bit_length() - 59)
+    if not lowest <= L <= 0:
+        raise ValueError(f"log2q {L} outside [{lowest}, 0] for {F} faces")
+    with torch.cuda.device(dev):
+        count = torch.empty(B, N, dtype=torch.int64, device=dev)
+        inside = torch.empty(B, N, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().hm_point_mesh_winding(_lib.ptr(points), _lib.ptr(verts), _lib.ptr(faces), B, N, V, F, L,
+                                                    _lib.ptr(count), _lib.ptr(inside), _lib.stream()), "hm_point_mesh_winding")
+    return count, inside, L
+
+
+def point_mesh_winding(points, verts, faces, log2q=None):
+    """Generalised winding number of points (B,N,3) against the triangle meshes verts (B,V,3), faces (F,3): the inside-outside
+    sign for meshes that need not be closed (no grad; csrc/winding.hip, the rules in include/homan_amd.h) -> {"count" (B,N)
+    int64 the signed solid angle of all faces in quanta of 2^log2q, summed exactly, "winding" (B,N) float64 = count * 2^log2q /
+    (4 pi), "inside" (B,N) int32 0 / 1: |winding| > 0.5, decided on the integers, "log2q"}.  log2q None = winding_log2q(F).
+    Skipped faces as `point_mesh_distance`, and faces of zero area; a non-finite point gets (0, 0).  For a point exactly on the
+    surface the values are deterministic but not meaningful.  Inputs are checked and moved as by `point_mesh_distance`; nothing
+    synchronises with the host; there is no CPU path."""
+    import math
+    count, inside, L = _winding_run(points, verts, faces, log2q)
+    with torch.cuda.device(count.device):
+        # (a true division: by a Python scalar torch multiplies with the reciprocal, which rounds differently)
+        winding = (count.double() * math.ldexp(1.0, L)) / torch.full((), 4.0 * math.pi, dtype=torch.float64, device=count.device)
+    return {"count": count, "winding": winding, "inside": inside, "log2q": L}
+
+
+def point_mesh_distance_signed(points, verts, faces, closest=False, sign="parity"):
+    """`point_mesh_distance` with a choice of the inside-outside rule.  sign="parity": that op, its keys and bits.
+    sign="winding": d2, face and closest are the search's bits unchanged, "inside" is `point_mesh_winding`'s (|w| > 0.5: meaningful
+    for open meshes too), and a key "winding" (B,N) float64 is added.  sign="auto": parity where `meshutils.mesh_topology` finds
+    the faces closed, else winding.  Any other string is a ValueError."""
+    from . import meshutils
+    rule = meshutils.resolve_sign(sign, faces)
+    out = point_mesh_distance(points, verts, faces, closest=closest)
+    if rule == "winding":
+        w = point_mesh_winding(points, verts, faces)
+        out["inside"], out["winding"] = w["inside"], w["winding"]
     return out
 
 

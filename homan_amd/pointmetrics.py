@@ -12,7 +12,7 @@ as contiguous fp32, and each call syncs with the host once.  There is no CPU pat
 import numpy as np
 import torch
 
-from . import constants, lib, ops
+from . import constants, lib, meshutils, ops
 
 
 def _one_hand_mesh_per_scene(verts_person, faces_person, scenes):
@@ -201,10 +201,13 @@ def get_volume_metrics(verts_person, verts_object, faces_person, faces_object, v
             "obj_volumes": volumes[hands].tolist()}
 
 
-def surface_frame_bytes(hands, hand_verts, obj_verts):
+def surface_frame_bytes(hands, hand_verts, obj_verts, sign="parity"):
     """device bytes one frame of `get_surface_metrics` holds at a time: per hand and direction the three per-point outputs of
-    `ops.point_mesh_distance` (d2, face, inside) and its merge words (8 + 4 bytes per point)"""
-    return int(hands) * (int(hand_verts) + int(obj_verts)) * 24
+    `ops.point_mesh_distance` (d2, face, inside) and its merge words (8 + 4 bytes per point); with the winding-number sign
+    (sign="winding", and "auto", which may choose it) the count and the flag of `ops.point_mesh_winding` on top (8 + 4)"""
+    if sign not in meshutils.SIGN_MODES:
+        raise ValueError(f"sign {sign!r} not in [parity|winding|auto]")
+    return int(hands) * (int(hand_verts) + int(obj_verts)) * (24 if sign == "parity" else 36)
 
 
 def _d2_at_most(dist):
@@ -234,7 +237,29 @@ def get_surface_metrics(verts_person, verts_object, faces_person, faces_object, 
       "contact_share"  the share of hand vertices with signed distance <= contact_thresh (inside counts), in double;
       "has_contact"    pen_depth > 0 or pen_depth_obj > 0 or min_dist <= contact_thresh.
     per_vertex adds "signed_dist" (B*hand_nb, Vh) float64, negative inside: the contact map.  Frames are walked in chunks whose
-    outputs fit `max_bytes`; a frame's values do not depend on the chunking.  The sign needs closed meshes.  No CPU path."""
+    outputs fit `max_bytes`; a frame's values do not depend on the chunking.  The sign is the ray parity, which needs closed
+    meshes: `get_surface_metrics_signed` takes open ones.  No CPU path."""
+    return get_surface_metrics_signed(verts_person, verts_object, faces_person, faces_object, contact_thresh, per_vertex,
+                                      max_bytes, "parity")
+
+
+def _inside(points, verts, faces, rule, searched):
+    """the inside flags (bool) of one direction: the search's parity, or the winding number's |w| > 0.5"""
+    if rule == "parity":
+        return searched["inside"] == 1
+    return ops._winding_run(points, verts, faces, None)[1] == 1
+
+
+def get_surface_metrics_signed(verts_person, verts_object, faces_person, faces_object, contact_thresh=0.005, per_vertex=False,
+                               max_bytes=256 << 20, sign="parity"):
+    """`get_surface_metrics` with a choice of the inside-outside rule, in both directions; distances are the same search's.
+    sign="parity": that function, its bits.  sign="winding": a point is inside a mesh iff its generalised winding number
+    exceeds 0.5 in magnitude (`ops.point_mesh_winding`, csrc/winding.hip): meaningful for meshes with holes, missing caps or
+    loose patches, and equal to parity on closed ones away from the surface.  sign="auto": per mesh, parity where
+    `meshutils.mesh_topology` finds its faces closed, else winding.  Each hand stays its own query.  Any other string is a
+    ValueError."""
+    if sign not in meshutils.SIGN_MODES:
+        raise ValueError(f"sign {sign!r} not in [parity|winding|auto]")
     verts_person, verts_object = torch.as_tensor(verts_person), torch.as_tensor(verts_object)
     _check_clouds(verts_person=verts_person, verts_object=verts_object)
     thresh = float(contact_thresh)
@@ -252,7 +277,7 @@ def get_surface_metrics(verts_person, verts_object, faces_person, faces_object, 
     obj_faces = np.asarray(torch.as_tensor(faces_object).cpu())
     obj_faces = obj_faces[0] if obj_faces.ndim == 3 else obj_faces
     Vh, Vo = verts_person.shape[1], verts_object.shape[1]
-    frame_bytes = surface_frame_bytes(hands, Vh, Vo)
+    frame_bytes = surface_frame_bytes(hands, Vh, Vo, sign)
     if frame_bytes > int(max_bytes):
         raise ValueError(f"one frame needs {frame_bytes} bytes of per-point outputs; max_bytes is {max_bytes}")
     person, obj = _on_gpu(verts_person, verts_object)
@@ -262,6 +287,8 @@ def get_surface_metrics(verts_person, verts_object, faces_person, faces_object, 
         hand_faces = [torch.from_numpy(np.ascontiguousarray(faces_person[k % faces_person.shape[0]], dtype=np.int32)).to(dev)
                       for k in range(hands)]
         object_faces = torch.from_numpy(np.ascontiguousarray(obj_faces, dtype=np.int32)).to(dev)
+        object_rule = meshutils.resolve_sign(sign, obj_faces)
+        hand_rules = [meshutils.resolve_sign(sign, faces_person[k % faces_person.shape[0]]) for k in range(hands)]
         per_hand = [person.reshape(scenes, hands, Vh, 3)[:, k].contiguous() for k in range(hands)]
         chunk = max(int(max_bytes) // frame_bytes, 1)
         rows, d2_maps, in_maps = [], [], []
@@ -275,15 +302,15 @@ def get_surface_metrics(verts_person, verts_object, faces_person, faces_object, 
             chunk_d2, chunk_in = [], []
             for k in range(hands):
                 to_obj = ops.point_mesh_distance(per_hand[k][sl], obj[sl], object_faces)
-                inside = to_obj["inside"] == 1
+                inside = _inside(per_hand[k][sl], obj[sl], object_faces, object_rule, to_obj)
                 deep = torch.maximum(deep, torch.where(inside, to_obj["d2"], torch.zeros_like(to_obj["d2"])).amax(1))
                 near = torch.minimum(near, to_obj["d2"].amin(1))
                 touching += (inside | (to_obj["d2"] <= d2_contact)).sum(1)
                 chunk_d2.append(to_obj["d2"])
                 chunk_in.append(inside)
                 to_hand = ops.point_mesh_distance(obj[sl], per_hand[k][sl], hand_faces[k])
-                deep_obj = torch.maximum(deep_obj, torch.where(to_hand["inside"] == 1, to_hand["d2"],
-                                                               torch.zeros_like(to_hand["d2"])).amax(1))
+                in_hand = _inside(obj[sl], per_hand[k][sl], hand_faces[k], hand_rules[k], to_hand)
+                deep_obj = torch.maximum(deep_obj, torch.where(in_hand, to_hand["d2"], torch.zeros_like(to_hand["d2"])).amax(1))
             rows.append(torch.stack([deep.double(), deep_obj.double(), near.double(), touching.double()]))
             if per_vertex:                                            # (frames, hands, Vh): frame-major, as verts_person
                 d2_maps.append(torch.stack(chunk_d2, 1))

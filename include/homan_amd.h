@@ -514,6 +514,44 @@ size_t hm_point_mesh_workspace_bytes(int B, int N, int F);
 int hm_point_mesh_distance(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, float* d2,
                            int* face_idx, int* inside, float* closest, void* workspace, hipStream_t stream);
 
+/* ------------------------------------------------------------------ generalised winding number (csrc/winding.hip)
+ * The inside-outside sign for meshes that are not closed (Jacobson et al. 2013): w = the signed solid angle of all faces seen
+ * from the point, over 4 pi; 1 inside a closed mesh, 0 outside, and it degrades smoothly where faces are missing.  The opt-in
+ * sign of the surface metrics (pointmetrics.get_surface_metrics_signed, sign="winding"); the parity rule above stays the default.
+ * Not in the reference tree: the rules below ARE the definition, pinned bit for bit by the NumPy restatement
+ * of tests/winding_ref.py.  Every operation is IEEE double from the fp32 inputs, without contraction, in the order written.
+ *
+ * points (B,N,3), verts (B,V,3), faces (F,3) as hm_point_mesh_distance.  Per point p and face (a, b, c):
+ *   A = (double)a - (double)p, B and C likewise; a dot product is (x*x + y*y) + z*z; la = sqrt(A.A), lb = sqrt(B.B), lc = sqrt(C.C);
+ *   B x C = (B_y C_z - B_z C_y, B_z C_x - B_x C_z, B_x C_y - B_y C_x); num = (A_x (B x C)_x + A_y (B x C)_y) + A_z (B x C)_z;
+ *   den = ((((la lb) lc + (A.B) lc) + (B.C) la) + (C.A) lb)                                    (Van Oosterom and Strackee 1983);
+ *   omega = 0 when num == 0 (a point in the face's plane or at one of its vertices), else 2 hm_atan2(num, den).
+ * hm_atan2(y, x) (csrc/hm_common.h) is a DEFINED function of plain double + - * / and compares, within 2^-44 rad of atan2:
+ *   mx = max(|x|, |y|), mn = min(|x|, |y|); 0 when mx == 0; u = (mn - mx) / (mn + mx) and base = pi/4 when mn > tan(pi/8) mx,
+ *   else u = mn / mx and base = 0; z = u u; q = c_19, then q = c_k + z q for k = 18 ... 1 with c_k the double nearest to
+ *   (-1)^k / (2k + 1); r = base + (u + (u z) q); r = pi/2 - r when |y| > |x|; r = pi - r when x < 0; r = -r when y < 0
+ *   (tan(pi/8) = 0.41421356237309503, pi/4 = 0.7853981633974483, pi/2 = 1.5707963267948966, pi = 3.141592653589793).
+ * Exact sum: every omega is rounded to the grid 2^log2q, to nearest with ties to even ((omega + magic) - magic in double with
+ * magic = 1.5 * 2^(52 + log2q)), and the quanta are added as a signed 64-bit INTEGER: count (B,N) depends neither on the order
+ * of the faces, nor on how they are dealt to workgroups, nor on the batch; two calls return the same bits.  No floating-point
+ * atomics.  w = count * 2^log2q / (4 pi).  log2q is the caller's: |omega| < 8, so log2q = max(-44, ceil(log2(F)) - 59)
+ * (ops.winding_log2q) keeps F addends below 2^62 quanta; admitted are max(-47, ceil(log2(F)) - 59) <= log2q <= 0 (below -47 the
+ * rounding add leaves its exact range).
+ * Sign: inside = 1 iff |count| > T with T = (long long)rint(ldexp(6.283185307179586, -log2q)), formed on the host in double:
+ * |w| > 0.5, decided in integers; the absolute value makes the rule indifferent to a mesh that is consistently wound the other
+ * way.  For a point exactly on the surface the result is deterministic and equal to the restatement, but not meaningful.
+ * Counts for nothing: a face that hm_point_mesh_distance skips (a vertex outside [0, V), a non-finite coordinate), and a face of
+ * zero area as the search defines it (the fp32 cross product (b - a) x (c - a) is exactly (0, 0, 0): the faces it treats as
+ * three segments).  A non-finite point gets count = 0, inside = 0.
+ * count: B*N signed 64-bit words, required - it is the accumulator: the call clears it on `stream` where workgroups share a
+ * point (the caller zero-fills nothing) and they merge with one 64-bit integer atomicAdd per point.  inside (B,N) int32, optional.
+ * No workspace.  Every launch goes on `stream`, nothing is allocated or synchronised.  HM_ERR_BAD_ARG, nothing enqueued, outputs
+ * untouched: B, N, V or F < 1, a NULL input, a NULL or misaligned count, a log2q outside the admitted range.  Every index is a
+ * 64-bit product of the int sizes.
+ * ALIGNMENT: count 8 bytes (typed void pointer: signed 64-bit words, targets of atomicAdd). */
+int hm_point_mesh_winding(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, int log2q,
+                          void* count, int* inside, hipStream_t stream);
+
 /* ------------------------------------------------------------------ surface contact loss (csrc/surfcontact.hip)
  * Attraction of the points outside a mesh and repulsion of the points inside it, each a tanh-saturated exact distance to the
  * surface (the loss of ObMan, Hasson et al. 2019, on the search above), with both gradients.  Not in the reference tree: the
