@@ -1419,3 +1419,178 @@ def surface_contact_terms(points, verts, ctx, weights=None, contact_thresh=0.010
         detail.update(inside=ctx.inside.clone(), loss=out, grad_points=ctx.grad_points.clone(),
                       grad_verts_attr=ctx.grad_verts_attr.clone(), grad_verts_rep=ctx.grad_verts_rep.clone())
     return detail
+
+
+# =============================================================================== mesh preparation (csrc/remesh.hip)
+LATTICE_OFFSET = np.float32(1.381966)        # cells between the lattice's origin and the box's lower corner
+LATTICE_RESOLUTIONS = (2, 256)               # admitted cells along the longest extent
+LATTICE_MAX_AXIS = 512                       # RM_MAX_AXIS of csrc/remesh.hip
+LATTICE_WORD, LATTICE_SCAN_TILE = 64, 2048   # corners per word of the packed field (= the emit kernels' row tile); rows per scan tile
+_LATTICE_REPORT_INTS = 73
+
+
+def _lattice_mesh(verts, faces):
+    """one mesh as host arrays -> (verts (V,3) fp32, faces (F,3) int64), checked"""
+    v = verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else np.asarray(verts)
+    if v.dtype.kind != "f" or v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1:
+        raise ValueError(f"verts: expected a non-empty float (V, 3) array, got {v.dtype} {v.shape}")
+    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+        raise ValueError(f"faces: expected a non-empty integer (F, 3) array, got {f.dtype} {f.shape}")
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int64)
+
+
+def lattice_box(verts, faces, resolution):
+    """The lattice of include/homan_amd.h for a source mesh, on the host -> (origin (3,) fp32, pitch fp32, dims (nx, ny, nz)
+    corners): h = max(hi - lo) / (float)R over the box of the vertices named by a face the search does not skip, origin =
+    lo - 1.381966f * h, floor((hi - lo) / h) + 5 corners per axis.  ValueError for R outside [2, 256], no valid face, a box
+    whose longest extent is not positive and finite."""
+    v, f = _lattice_mesh(verts, faces)
+    R = int(resolution)
+    if R != resolution or not LATTICE_RESOLUTIONS[0] <= R <= LATTICE_RESOLUTIONS[1]:
+        raise ValueError(f"resolution {resolution!r} not an integer in [{LATTICE_RESOLUTIONS[0]}, {LATTICE_RESOLUTIONS[1]}]")
+    in_range = ((f >= 0) & (f < len(v))).all(1)
+    ok = in_range & np.isfinite(v[np.where(in_range[:, None], f, 0)]).all((1, 2))
+    if not ok.any():
+        raise ValueError("the mesh has no face with in-range, finite vertices")
+    used = v[np.unique(f[ok])]
+    lo, hi = used.min(0), used.max(0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        ext = hi - lo
+        h = np.float32(ext.max()) / np.float32(R)
+        if not (np.isfinite(h) and h > 0):
+            raise ValueError(f"degenerate bounding box: extents {ext.tolist()}")
+        origin = lo - LATTICE_OFFSET * h
+        dims = tuple(int(n) + 5 for n in np.floor(ext / h))
+    if not np.isfinite(origin).all():
+        raise ValueError("the lattice's origin is not finite")
+    return origin, h, dims
+
+
+def _lattice_args(origin, pitch):
+    o = np.asarray(origin, dtype=np.float64).reshape(-1)
+    with np.errstate(over="ignore"):
+        o32, h = o.astype(np.float32), np.float32(pitch)
+    if o.shape != (3,) or not np.isfinite(o32).all():
+        raise ValueError(f"origin: expected three finite numbers, got {origin!r}")
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError(f"pitch {pitch!r} is not positive and finite in fp32")
+    return o32, h
+
+
+def lattice_signs(verts, faces, resolution, sign="winding"):
+    """The sign lattice of a source mesh (csrc/remesh.hip, csrc/winding.hip; the rules in include/homan_amd.h): verts (V,3),
+    faces (F,3) of ONE mesh, `resolution` cells along its longest extent -> {"inside" (nz, ny, nx) int32 on the device: the flag
+    of every corner by sign="winding" (|w| > 0.5: sources that need not be closed) or "parity" (closed sources), "origin" (3,)
+    fp32 and "pitch" fp32 on the host, "dims" (nx, ny, nz), "corners" (nz ny nx, 3) fp32 the positions}.  The box is formed
+    on the host (`lattice_box`); the search is brute force over every corner.  No grad, no CPU path."""
+    if sign not in ("winding", "parity"):
+        raise ValueError(f"sign {sign!r} not in [winding|parity]")
+    v, f = _lattice_mesh(verts, faces)
+    origin, h, (nx, ny, nz) = lattice_box(v, f, resolution)
+    if not torch.cuda.is_available():
+        raise _lib.HomanAmdError("homan_amd.ops.lattice_signs needs the GPU (there is no CPU fallback)")
+    dev = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        pts = torch.empty(nz * ny * nx, 3, device=dev)
+        _lib.check(_lib.lib().hm_lattice_corners(nx, ny, nz, float(origin[0]), float(origin[1]), float(origin[2]), float(h),
+                                                 _lib.ptr(pts), _lib.stream()), "hm_lattice_corners")
+        vt = torch.from_numpy(v).to(dev)[None]
+        if sign == "winding":
+            inside = _winding_run(pts[None], vt, f, None)[1]
+        else:
+            inside = point_mesh_distance(pts[None], vt, f)["inside"]
+    return {"inside": inside.view(nz, ny, nx), "origin": origin, "pitch": h, "dims": (nx, ny, nz), "corners": pts}
+
+
+def _lattice_field(inside, who):
+    """the argument checks shared by the sign-field ops -> (the field as a tensor, (nx, ny, nz))"""
+    t = inside if isinstance(inside, torch.Tensor) else torch.from_numpy(np.array(inside))
+    if t.dim() != 3 or t.is_floating_point() or t.is_complex():
+        raise ValueError(f"inside: expected (nz, ny, nx) integers or booleans, got {t.dtype} {tuple(t.shape)}")
+    nz, ny, nx = (int(n) for n in t.shape)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) > LATTICE_MAX_AXIS:
+        raise ValueError(f"inside: every axis must have 2 ... {LATTICE_MAX_AXIS} corners, got {(nz, ny, nx)}")
+    return t, (nx, ny, nz)
+
+
+def _surface_nets_counted(t, dims, who):
+    """hm_lattice_repair and hm_surface_nets_count on a checked field, and the ONE host read -> (the device buffers for
+    hm_surface_nets_emit, host = [passes, corners, status, ..., cells, x-, y-, z-edges])"""
+    if not torch.cuda.is_available():
+        raise _lib.HomanAmdError(f"homan_amd.ops.{who} needs the GPU (there is no CPU fallback)")
+    nx, ny, nz = dims
+    dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    handle = _lib.lib()
+    with torch.cuda.device(dev):
+        flags = (t.detach() != 0).to(device=dev, dtype=torch.int32).contiguous()
+        words = handle.hm_lattice_words(nx, ny, nz)
+        bits = torch.empty(2 * words, dtype=torch.int64, device=dev)
+        cell_bits = torch.empty(words, dtype=torch.int64, device=dev)
+        offsets = torch.empty(4 * ny * nz, dtype=torch.int32, device=dev)
+        report = torch.empty(_LATTICE_REPORT_INTS + 4, dtype=torch.int32, device=dev)
+        totals = report[_LATTICE_REPORT_INTS:]
+        _lib.check(handle.hm_lattice_repair(_lib.ptr(flags), nx, ny, nz, _lib.ptr(bits), _lib.ptr(report), _lib.stream()),
+                   "hm_lattice_repair")
+        _lib.check(handle.hm_surface_nets_count(_lib.ptr(bits), nx, ny, nz, _lib.ptr(cell_bits), _lib.ptr(offsets),
+                                                _lib.ptr(totals), _lib.stream()), "hm_surface_nets_count")
+        host = report.cpu().tolist()                                       # the one host read
+    if host[2]:
+        raise _lib.HomanAmdError(f"{who}: the checkerboard repair did not settle in 64 passes")
+    return (dev, bits, cell_bits, offsets, totals), host
+
+
+def surface_nets_count(inside):
+    """The counts of `surface_nets` without its outputs (hm_lattice_repair + hm_surface_nets_count, one host read): what the
+    budget search of `meshprep.make_watertight` probes with -> {"cells": vertices the field would give, "triangles",
+    "repair_passes", "repaired_corners"}.  Arguments and errors as `surface_nets`."""
+    t, dims = _lattice_field(inside, "surface_nets_count")
+    _, host = _surface_nets_counted(t, dims, "surface_nets_count")
+    return {"cells": host[-4], "triangles": 2 * sum(host[-3:]), "repair_passes": host[0], "repaired_corners": host[1]}
+
+
+def surface_nets(inside, origin, pitch):
+    """Surface nets on a lattice of signs (csrc/remesh.hip, the rules in include/homan_amd.h): inside (nz, ny, nx) integers or
+    booleans, non-zero = inside (tensor or array; the outermost layer is forced outside), corner (i, j, k) at origin +
+    (float)index * pitch -> {"vertices" (V,3) fp32, "faces" (T,3) int32 on the device: closed, oriented, normals outward,
+    "repair_passes", "repaired_corners": the checkerboard repair's counts, "cells" = V}.  The output is a function of the field
+    alone, the same bits on every call.  ONE host read (the repair's report and the counts) sizes the outputs.  No grad, no CPU
+    path; a field the repair cannot settle in 64 passes raises HomanAmdError."""
+    t, (nx, ny, nz) = _lattice_field(inside, "surface_nets")
+    o, h = _lattice_args(origin, pitch)
+    (dev, bits, cell_bits, offsets, totals), host = _surface_nets_counted(t, (nx, ny, nz), "surface_nets")
+    n_vertices, n_faces = host[-4], 2 * sum(host[-3:])
+    with torch.cuda.device(dev):
+        vertices = torch.empty(n_vertices, 3, device=dev)
+        faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().hm_surface_nets_emit(_lib.ptr(bits), _lib.ptr(cell_bits), _lib.ptr(offsets), _lib.ptr(totals), nx,
+                                                   ny, nz, float(o[0]), float(o[1]), float(o[2]), float(h), n_vertices, n_faces,
+                                                   _lib.ptr(vertices) if n_vertices else None,
+                                                   _lib.ptr(faces) if n_faces else None, _lib.stream()), "hm_surface_nets_emit")
+    return {"vertices": vertices, "faces": faces, "repair_passes": host[0], "repaired_corners": host[1], "cells": n_vertices}
+
+
+def lattice_snap(lattice_vertices, closest, d2, pitch, snap_limit):
+    """The snap of include/homan_amd.h: per vertex `closest` iff d2 <= (snap_limit * snap_limit) * (pitch * pitch) in fp32, else
+    its lattice position -> (vertices (n,3) fp32, snapped (n,) int32); device tensors in, new device tensors out."""
+    _, h = _lattice_args((0.0, 0.0, 0.0), pitch)
+    with np.errstate(over="ignore"):
+        sl = np.float32(snap_limit)
+    if not (np.isfinite(sl) and sl > 0):
+        raise ValueError(f"snap_limit {snap_limit!r} is not positive and finite in fp32")
+    n = lattice_vertices.shape[0] if isinstance(lattice_vertices, torch.Tensor) and lattice_vertices.dim() == 2 else -1
+    for name, x, shape in (("lattice_vertices", lattice_vertices, (n, 3)), ("closest", closest, (n, 3)), ("d2", d2, (n,))):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != shape or n < 0:
+            raise ValueError(f"{name}: expected an fp32 tensor of shape {shape}, got {getattr(x, 'dtype', type(x))} "
+                             f"{tuple(getattr(x, 'shape', ()))}")
+    if not lattice_vertices.is_cuda:
+        raise _lib.HomanAmdError("homan_amd.ops.lattice_snap needs device tensors (there is no CPU fallback)")
+    dev = lattice_vertices.device
+    with torch.cuda.device(dev):
+        out = torch.empty(n, 3, device=dev)
+        snapped = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            _lib.check(_lib.lib().hm_lattice_snap(_lib.ptr(lattice_vertices.contiguous()), _lib.ptr(closest.contiguous()),
+                                                  _lib.ptr(d2.contiguous()), n, float(sl), float(h), _lib.ptr(out),
+                                                  _lib.ptr(snapped), _lib.stream()), "hm_lattice_snap")
+    return out, snapped

@@ -552,6 +552,72 @@ int hm_point_mesh_distance(const float* points, const float* verts, const int* f
 int hm_point_mesh_winding(const float* points, const float* verts, const int* faces, int B, int N, int V, int F, int log2q,
                           void* count, int* inside, hipStream_t stream);
 
+/* ------------------------------------------------------------------ mesh preparation: surface nets on a sign lattice (csrc/remesh.hip)
+ * From a raw object mesh (holes, missing caps, any face count) to the closed, oriented mesh of about a thousand vertices that the
+ * fits, the collision grid, the voxeliser and the parity sign assume: homan_amd/meshprep.py make_watertight / simplify_mesh, in
+ * place of the reference's external ManifoldPlus + ACVD stage (meshprocess/simplifymesh.py).  The rules below ARE the definition
+ * (DESIGN.md section 7), pinned bit for bit by the NumPy restatement of tests/meshprep_ref.py.  The topology is a pure function of
+ * the sign field (integers only); every floating-point operation is fp32 IEEE without contraction.
+ *
+ * Lattice.  Corners (i, j, k), 0 <= i < nx and so on, at origin + (float)index * h per axis (one multiply, one add); a flag or a
+ * position of corner (i, j, k) is element (k * ny + j) * nx + i.  For a source mesh (ops.lattice_signs): lo, hi = the fp32 bounding
+ * box of the vertices named by a face that hm_point_mesh_distance does not skip; R cells along the longest extent, 2 <= R <= 256:
+ * h = max(hi - lo) / (float)R, refused unless positive and finite; origin = lo - 1.381966f * h (the offset keeps axis-aligned
+ * planes at simple fractions of the box off the lattice planes); n = (int)floorf((hi - lo) / h) + 5 corners per axis, so that two
+ * corner layers lie below lo and the last two at least 0.6 h and 1.6 h above hi: the outermost layer is strictly outside the box.
+ * Signs.  A corner is inside iff its flag is non-zero and it is not on the outermost layer (an index 0 or n - 1), which is forced
+ * outside.  The flags are the caller's: hm_point_mesh_winding's `inside` (|w| > 0.5) for sources that need not be closed, the
+ * parity of hm_point_mesh_distance, or any field of one's own.
+ * Repair.  A unit lattice face whose corners are a checkerboard (s00 == s11 != s10 == s01) would put four quads on one mesh edge.
+ * A pass reads the old field and sets all four corners of every such face (Jacobi: new = old OR marks, no order); passes repeat
+ * until one changes nothing.  report[0] = the number of passes that changed something, report[1] = the corners set, report[2] = 1
+ * if pass 65 still changed something (the caller's error: the field is not settled), else 0.  The outer layer is never set: a
+ * face that touches it has two adjacent corners on it.  Two inside corners diagonally opposite across a CELL are left alone: they
+ * give a pinched vertex (two sheets meeting in a point), not an edge with four faces.  With the repair every edge of the output
+ * has exactly two faces, of opposite direction: closed and oriented.
+ * Vertices.  A cell (ci, cj, ck), corners (ci..ci+1, cj..cj+1, ck..ck+1), is active iff its 8 corners are not all equal; its
+ * vertex index is its rank among the active cells in row-major order, ci fastest, then cj, then ck.  With S = the sum over its
+ * sign-changing edges of the edge's midpoint in half-cell units (an x-edge from corner (i, j, k): (2i + 1, 2j, 2k); integers, so
+ * exact and free of order) and n their count: position_a = origin_a + ((float)S_a / (float)n) * (0.5f * h).
+ * Faces.  Every lattice edge whose two ends differ emits one quad.  For an edge along axis a from base corner p, the cells are p
+ * shifted by (-1,-1), (0,-1), (0,0), (-1,0) along the axes ((a + 1) % 3, (a + 2) % 3): c0, c1, c2, c3 when p is inside, and the
+ * reversed cycle c3, c2, c1, c0 when p is outside, so that normals point from inside to outside and the signed volume is positive;
+ * the quad (q0, q1, q2, q3) is the triangles (q0, q1, q2), (q0, q2, q3).  Order: all x-edges, then all y-edges, then all z-edges,
+ * each by base corner in row-major order, i fastest.  The order comes from per-row popcounts and an exclusive scan over the rows:
+ * no atomic decides a position, two calls give the same bits.
+ * Snap.  out = closest (hm_point_mesh_distance's) iff d2 <= (snap_limit * snap_limit) * (h * h), compared in fp32, else the lattice
+ * position; snap_limit is in cells, default the cell diagonal 1.7320508f (meshprep.SNAP_LIMIT).  Over a hole the half level of the
+ * winding number spans the gap like a film; the limit keeps the film's vertices on the film instead of collapsing onto the rim.
+ * Left out: feature-preserving placement (no QEF, no sharp edges), decimation other than through h, components thinner than a
+ * cell (they vanish).  The sign search stays brute force over every corner.
+ *
+ * The packed field: corner (i, j, k) is bit i & 63 of 64-bit word (k * ny + j) * W + (i >> 6), W = ceil(nx / 64);
+ * hm_lattice_words = ny * nz * W (-1 for dimensions that are refused).  Admitted: 2 <= nx, ny, nz <= 512, so that the
+ * largest possible output, 6 nx ny nz triangles, and every count and index fit an int.
+ * hm_lattice_repair: flags (nz, ny, nx) int32 -> bits: 2 * hm_lattice_words words, the first half is the repaired field (the
+ * second is the passes' other buffer); report: 73 ints, cleared by the call ([8 + p] = corners set by pass p).  Atomics: one
+ * integer add per changed word into the pass's counter.
+ * hm_surface_nets_count: bits -> cell_bits (hm_lattice_words words: the active cells in the field's layout), row_offsets
+ * (4 * ny * nz ints: per row k * ny + j the exclusive offsets of its active cells, then of the x-, y-, z-edges it bases) and
+ * totals (4 ints: active cells, x-, y-, z-edges).  vertices = totals[0], triangles = 2 * (totals[1] + totals[2] + totals[3]).
+ * hm_surface_nets_emit: vertices (max_vertices, 3) fp32 and triangles (max_triangles, 3) int32; the caller sizes them from the
+ * totals (one host read); an element beyond a capacity is not written; a capacity of 0 skips that output (its pointer may be
+ * NULL).  hm_lattice_snap: lattice, closest (n, 3), d2 (n) -> out (n, 3), snapped (n) int32 0 / 1, optional; n = 0 is HM_OK.
+ * Every launch goes on `stream`; nothing is allocated or synchronised.  HM_ERR_BAD_ARG, nothing enqueued, outputs untouched: a
+ * NULL pointer (other than the optional ones), a dimension outside the admitted range, a non-finite origin, an h or snap_limit
+ * that is not positive and finite, a negative capacity or n, a misaligned bits or cell_bits.
+ * ALIGNMENT: bits and cell_bits 8 bytes (typed void pointers: 64-bit words). */
+long hm_lattice_words(int nx, int ny, int nz);
+int hm_lattice_corners(int nx, int ny, int nz, float ox, float oy, float oz, float h, float* points, hipStream_t stream);
+int hm_lattice_repair(const int* flags, int nx, int ny, int nz, void* bits, int* report, hipStream_t stream);
+int hm_surface_nets_count(const void* bits, int nx, int ny, int nz, void* cell_bits, int* row_offsets, int* totals,
+                          hipStream_t stream);
+int hm_surface_nets_emit(const void* bits, const void* cell_bits, const int* row_offsets, const int* totals, int nx, int ny, int nz,
+                         float ox, float oy, float oz, float h, int max_vertices, int max_triangles, float* vertices,
+                         int* triangles, hipStream_t stream);
+int hm_lattice_snap(const float* lattice, const float* closest, const float* d2, long n, float snap_limit, float h, float* out,
+                    int* snapped, hipStream_t stream);
+
 /* ------------------------------------------------------------------ surface contact loss (csrc/surfcontact.hip)
  * Attraction of the points outside a mesh and repulsion of the points inside it, each a tanh-saturated exact distance to the
  * surface (the loss of ObMan, Hasson et al. 2019, on the search above), with both gradients.  Not in the reference tree: the
