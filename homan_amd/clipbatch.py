@@ -80,6 +80,40 @@ class ClipBatch(nn.Module):
             self.collision_ctx = ops.CollisionContext(m0.mano_model.closed_faces, m0.faces_object[0], self.B, 778,
                                                       m0.verts_object_og.shape[1], dev)
         self.reduce_ws = ClipReduceWorkspace(dev, self.C)
+        self._depth_state = None
+
+    def depth_contexts(self):
+        """(object raster context, hand raster context, object instance masks u8, hand instance masks u8) of the ordinal depth
+        term over all frames of the batch (one hand per frame; built once).  One clip: the model's own.  Several: the two renders
+        run over all frames at once, the ordinal term (it normalises over ONE clip) per clip on its slice of the images."""
+        if self._depth_state is None and self.C == 1:
+            self._depth_state = self.models[0].depth_contexts()
+        elif self._depth_state is None:
+            m0, size, dev = self.models[0], int(self.image_size), self.translations_object.device
+            m_o, m_h = (torch.cat(ms).contiguous() for ms in zip(*(m._depth_masks() for m in self.models)))
+            self._depth_state = (ops.SilhouetteContext(m0.faces_object[:1].expand(self.B, -1, -1), m0.verts_object_og.shape[1],
+                                                       self.B, size, dev),
+                                 ops.SilhouetteContext(m0.faces_hand[:1].expand(self.B, -1, -1), 778, self.B, size, dev), m_o, m_h)
+        return self._depth_state
+
+    def load_clips(self, clip_inputs):
+        """`clip_inputs`: one dict of HOMan data arguments per clip of the batch (what `collate_inputs` returns, + camintr), clips
+        of the shapes and topology the batch was built for: HOMan.load_clip per model, then everything the BATCH keeps of its
+        clips - the concatenated buffers (Parameters are views of its storage), per-clip normalisers, depth masks, raster state."""
+        if len(clip_inputs) != self.C:
+            raise ValueError(f"load_clips: {len(clip_inputs)} clips for a batch of {self.C}")
+        with torch.no_grad():
+            for c, (one, kw) in enumerate(zip(self.models, clip_inputs)):
+                one.load_clip(**kw)
+                if self.C > 1:
+                    for k, cat in self.named_buffers(recurse=False):
+                        self.clip_slice(cat, c).copy_(getattr(one, k))
+                    self.keep_sum[c:c + 1].copy_(one.losses.keep_sum)
+                    if self._depth_state is not None:
+                        for cat, src in zip(self._depth_state[2:], one._depth_masks()):
+                            self.clip_slice(cat, c).copy_(src)
+            if self.C > 1:
+                self.sil_ctx.invalidate_outputs()
 
     def _adopt(self, name, t):
         if isinstance(t, nn.Parameter):

@@ -304,31 +304,20 @@ class FusedStepper:
         side = m.models[0].hand_sides[0]
         self.mctx = m.mano_model.ctx_mean if side == "right" else m.mano_model._left_ctx(False)      # (see ManoModel)
         self.hand_order = _morton_order(self.mctx.tensors[0]).to(dev)
-        # bounding spheres, in MESH space, of the groups of 64 vertices in that order, per frame (a clip's frames share one mesh,
-        # the clips of a batch need not): centre = mean, radius = farthest vertex.  The search carries them into camera space
-        # with the frame's rigid transform instead of reducing the transformed vertices of every group in every workgroup.
-        with torch.no_grad():
-            # (repeats of a real vertex pad the last group: they change nothing but the mean, and are masked out of it)
-            self.obj_spheres = self._group_spheres()                                         # (B, ng, 4)
+        self._install_clip_constants()       # sil_K / sil_keep / sil_ref, obj_spheres
         self.pooled = f(B, m.sil_ctx.S, m.sil_ctx.S)
-        # silhouettes at a size off the kernels' 32-pixel tile grid (the reference's REND_SIZE is 256): rendered on the next
-        # multiple with the first two rows of K rescaled and the masks padded with keep = 0 (ops.SilhouetteContext); all three
-        # are constants of the fit, built once; eps of the pseudo-gradient in the padded grid's NDC units
-        sx = m.sil_ctx
-        self.sil_K = sx.K_eff(m.camintr_rois_object).contiguous()
-        self.sil_keep, self.sil_ref = sx.pad(m.keep_mask_object), sx.pad(m.ref_mask_object)
         self.up_sil, self.up_inter = torch.tensor([w["loss_sil_obj"]], device=dev), torch.tensor([w["loss_inter"]], device=dev)
         if self.on["depth"] and h > 1:
             # two hands per frame: the three layers [object, hand 0, hand 1] of reference homan.py:384-419, every unordered pair
             # through the two-layer kernels, one normaliser for the scene (lossutils.py:133-169; ops.ordinal_depth_loss_layers is
             # the autograd form of what _forward_backward_hands issues)
-            ctx_o, ctx_hs, m_o, m_hs = m.models[0]._depth_contexts_hands()
-            if ctx_o.padded:
+            ctxs, masks = m.models[0].depth_layers()
+            if ctxs[0].padded:
                 raise NotImplementedError("the fused loop renders the depth images at image_size % 32 == 0; other sizes: "
                                           "mode='graph' or 'eager'")
-            self.dlayers = [(ctx_o, Vo, m_o)] + [(ctx_hs[i], Vh, m_hs[i]) for i in range(h)]
+            self.dlayers = list(zip(ctxs, [Vo] + [Vh] * h, masks))
             self.dpairs = [(a, b) for a in range(h + 1) for b in range(a + 1, h + 1)]
-            Sd = ctx_o.S
+            Sd = ctxs[0].S
             self.dl_sil, self.dl_dep = [f(B, Sd, Sd) for _ in self.dlayers], [f(B, Sd, Sd) for _ in self.dlayers]
             self.dl_g = [f(B, Sd, Sd) for _ in self.dlayers]
             self.dp_part, self.dp_rec = [f(B * 8) for _ in self.dpairs], [f(8) for _ in self.dpairs]
@@ -339,19 +328,7 @@ class FusedStepper:
         elif self.on["depth"]:
             # ordinal depth term (reference homan.py:384-419, opt-in): object and hand rendered with depth at the full-image
             # camera, the pair-wise ordinal loss, and its gradient back through both depth images to the camera-space vertices
-            if C == 1:
-                self.dctx = m.models[0].depth_contexts()
-            else:
-                # a clip batch: the two depth renders run over all frames at once, the ordinal term (it normalises over ONE
-                # clip: pairs, mask counts) per clip on its slice of the images
-                m0_, size = m.models[0], int(m.image_size)
-                for one in m.models:
-                    if tuple(one.masks_object.shape[1:]) != (size, size) or tuple(one.masks_human.shape[1:]) != (size, size):
-                        raise NotImplementedError("ordinal depth: instance masks must be (B, image_size, image_size)")
-                self.dctx = (ops.SilhouetteContext(m0_.faces_object[:1].expand(B, -1, -1), Vo, B, size, dev),
-                             ops.SilhouetteContext(m0_.faces_hand[:1].expand(B, -1, -1), 778, B, size, dev),
-                             torch.cat([(one.masks_object != 0).to(torch.uint8) for one in m.models]).contiguous(),
-                             torch.cat([(one.masks_human != 0).to(torch.uint8) for one in m.models]).contiguous())
+            self.dctx = m.depth_contexts()
             ctx_o, ctx_h = self.dctx[0], self.dctx[1]
             if ctx_o.padded:
                 raise NotImplementedError("the fused loop renders the depth images at image_size % 32 == 0; other sizes: "
@@ -437,51 +414,52 @@ class FusedStepper:
     def reload(self, clip_inputs):
         """`clip_inputs`: one dict of HOMan data arguments per clip of the batch (what `collate_inputs` returns, + camintr),
         clips of exactly the shapes and topology this stepper was built for.  Everything that depends on the clip is copied in
-        place - Parameters, buffers, per-clip normalisers, the search's bounding spheres - and everything that depends on the
-        FIT is reset - Adam moments, step counter, loss slots -; buffers, workspaces, streams and the captured hipGraph are
-        reused as they are.  The next `run(steps)` is the fit of the new clips, bit-identical to the fit a freshly built
-        stepper would make (tests/test_clip_fitter_gpu.py)."""
-        m = self.model
-        if len(clip_inputs) != m.C:
-            raise ValueError(f"reload: {len(clip_inputs)} clips for a stepper of {m.C}")
-        from .clipbatch import _PER_CLIP, _PER_FRAME
+        place (ClipBatch.load_clips, then the stepper's own constants) and everything that depends on the FIT is reset;
+        buffers, workspaces, streams and the captured hipGraph are reused as they are.  The next `run(steps)` is the fit of the
+        new clips, bit-identical to the fit a freshly built stepper would make (tests/test_clip_fitter_gpu.py).
+        Carried across clips on purpose, none of it able to change a result:
+          nn_seed   per frame the vertex pair that held the minimum at the last launch.  The search evaluates that pair's
+                    distance at the CURRENT vertices: the distance of a real pair, so an upper bound of the minimum it then finds
+                    exactly (nn_min_body, csrc/pair_bodies.h); indices out of range are ignored.  Any pair prunes correctly.
+          d_flags   written in full (1 or 0 per segment) by hm_ordinal_depth_bwd_flags of an iteration BEFORE that iteration's
+                    hm_depth_bwd_sparse reads them (csrc/raster_depth.hip): the previous clip's are never read.
+          the raster's cost order (calibrate(), hm_tune_raster_reorder)   a permutation of the (frame, region) workgroups of
+                    k_raster_fwd, each of which writes its own region's pixels only (csrc/raster_fwd.hip): any order, same image."""
+        self.model.load_clips(clip_inputs)
+        self._install_clip_constants()
+        self._reset_fit()
+        if self.shared_scale:
+            self._sync_shared_scale_start()
+
+    def _install_clip_constants(self):
+        """What the stepper itself derives from the clips' data: assigned at construction, copied in place on reload.
+        sil_K / sil_keep / sil_ref: silhouettes at a size off the kernels' 32-pixel tile grid (the reference's REND_SIZE is 256)
+        are rendered on the next multiple, with the first two rows of K rescaled and the masks padded with keep = 0
+        (ops.SilhouetteContext); on the grid they ARE the batch's tensors.  obj_spheres: see _group_spheres."""
+        m, sx = self.model, self.model.sil_ctx
         with torch.no_grad():
-            for c, (one, kw) in enumerate(zip(m.models, clip_inputs)):
-                one.load_clip(**kw)
-                if m.C > 1:     # the batch's own concatenated copies of the BUFFERS (Parameters are views of its storage)
-                    for k in _PER_FRAME + _PER_CLIP:
-                        if hasattr(m, k) and not isinstance(getattr(m, k), torch.nn.Parameter):
-                            m.clip_slice(getattr(m, k), c).copy_(getattr(one, k))
-                    m.keep_sum[c:c + 1].copy_(one.losses.keep_sum)
-            if m.C > 1:
-                m.sil_ctx.invalidate_outputs()
-            sx = m.sil_ctx
-            if sx.padded:       # (unpadded: these ARE the model's tensors)
-                self.sil_K.copy_(sx.K_eff(m.camintr_rois_object))
-                self.sil_keep.copy_(sx.pad(m.keep_mask_object))
-                self.sil_ref.copy_(sx.pad(m.ref_mask_object))
-            self.obj_spheres.copy_(self._group_spheres())
-            if self.on["depth"] and self.h == 1 and m.C == 1:     # (two hands: the layers' masks are the model's own tensors, copied in place)
-                self.dctx = m.models[0].depth_contexts()
-            elif self.on["depth"] and self.h == 1:
-                # a clip batch: the instance masks of the depth term are the stepper's own concatenation of the clips' masks
-                CL = m.clip_len
-                for c, one in enumerate(m.models):
-                    self.dctx[2][c * CL:(c + 1) * CL].copy_((one.masks_object != 0).to(torch.uint8))
-                    self.dctx[3][c * CL:(c + 1) * CL].copy_((one.masks_human != 0).to(torch.uint8))
-            for st_m, st_v in self.opt.state:
-                st_m.zero_()
-                st_v.zero_()
-            self.opt.step_t.zero_()
-            self.vals.zero_()
-            for p in m.parameters():
-                if p.grad is not None:
-                    p.grad.zero_()
-            if self.shared_scale:
-                self._sync_shared_scale_start()
+            new = dict(sil_K=sx.K_eff(m.camintr_rois_object).contiguous(), sil_keep=sx.pad(m.keep_mask_object),
+                       sil_ref=sx.pad(m.ref_mask_object), obj_spheres=self._group_spheres())
+            for name, t in new.items():
+                own = getattr(self, name, None)
+                if own is None:
+                    setattr(self, name, t)
+                elif own.data_ptr() != t.data_ptr():
+                    own.copy_(t)
+
+    def _reset_fit(self):
+        """everything that belongs to the fit, not to the clip: Adam moments and step counter, loss slots, gradients"""
+        self.opt.reset()
+        self.vals.zero_()
+        for p in self.model.parameters():
+            if p.grad is not None:
+                p.grad.zero_()
 
     def _group_spheres(self):
-        """bounding spheres, in MESH space, of the groups of 64 object vertices in `obj_order`, per frame: (B, groups, 4)"""
+        """Bounding spheres, in MESH space, of the groups of 64 object vertices in `obj_order`, per frame (a clip's frames share
+        one mesh, the clips of a batch need not): (B, groups, 4), centre = mean, radius = farthest vertex.  The search carries
+        them into camera space with the frame's rigid transform instead of reducing the transformed vertices of every group in
+        every workgroup.  (Repeats of a real vertex pad the last group: masked out of the mean, they change nothing.)"""
         m, Vo, B = self.model, self.Vo, self.B
         ng = (Vo + 63) // 64
         vs = m.verts_object_og.detach()[:, self.obj_order.long()]

@@ -50,6 +50,52 @@ def weakcam_persp_trans(cams, K, image_size=640, reference_depth=1.0):
     return torch.stack([tx, ty, tz.expand_as(tx)], 1).unsqueeze(1)
 
 
+def clip_tensors(translations_object, rotations_object, verts_object_og, translations_hand, rotations_hand, verts_hand_og,
+                 ref_verts2d_hand, mano_trans, mano_rot, mano_betas, mano_pca_pose, masks_object, masks_hand,
+                 camintr_rois_object, camintr_rois_hand, target_masks_object, target_masks_hand, cams_hand=None, camintr=None,
+                 int_scale_init=1.0, hand_proj_mode="persp", device=None, **_not_clip_data):
+    """The data arguments of the constructor (reference homan/homan.py:27-60) -> ordered {name: tensor} of everything in a
+    model that depends on the clip, in the form the model stores it (:62-166; in the constructor's registration order).  The ONE
+    place where raw clip inputs are converted: HOMan.__init__ registers these, HOMan.load_clip copies them in place.  Raises
+    the ortho refusals on the host input (forward may run inside a stream capture).  Without `device` nothing touches a
+    device; with it, what is DERIVED (mask comparisons, constants) is formed there - the clip's own arrays stay where the
+    caller has them, so that the consumer's copy is their one transfer."""
+    f32 = lambda t: torch.as_tensor(t).detach().float()
+    rot6d = lambda r: (matrix_to_rot6d(r) if r.shape[-1] == 3 else r).contiguous()
+    const = lambda shape, value: torch.full(tuple(shape), float(value), device=device)
+    if cams_hand is None:
+        if hand_proj_mode == "ortho":
+            raise ValueError("hand_proj_mode='ortho' needs cams_hand (scaled-orthographic [s, tx, ty] per hand, s != 0)")
+        cams_hand = torch.zeros(translations_hand.shape[0], 3)
+    elif hand_proj_mode == "ortho" and bool((f32(cams_hand).reshape(-1, 3)[:, 0] == 0).any()):
+        raise ValueError("hand_proj_mode='ortho': cams_hand holds a zero scale (the translation is f / s)")
+    tmo, tmh = (f32(t) if device is None else f32(t).to(device, non_blocking=True)
+                for t in (target_masks_object, target_masks_hand))
+    # (no intrinsics = the reference's default, homan.py:156-158 - for a clip loaded into a resident model too, NOT the previous
+    #  clip's; one matrix serves every frame)
+    camintr = f32([[[1, 0, 0.5], [0, 1, 0.5], [0, 0, 1]]] if camintr is None else camintr)
+    camintr = camintr.unsqueeze(0) if camintr.dim() == 2 else camintr
+    if camintr.shape[0] == 1:
+        camintr = camintr.expand(translations_object.shape[0], 3, 3)
+    masks_object = torch.as_tensor(masks_object).detach()
+    out = dict(
+        translations_object=f32(translations_object), rotations_object=rot6d(f32(rotations_object)),
+        verts_object_og=f32(verts_object_og), translations_hand=f32(translations_hand),
+        rotations_hand=rot6d(f32(rotations_hand)), cams_hand=f32(cams_hand), mano_pca_pose=f32(mano_pca_pose),
+        mano_rot=f32(mano_rot), mano_trans=f32(mano_trans), mano_betas=const(f32(mano_betas).shape, 0),      # (betas start at zero, :108)
+        int_scales_hand=const((1,), int_scale_init), verts_hand_og=f32(verts_hand_og), ref_verts2d_hand=f32(ref_verts2d_hand),
+        # (reference :122 wraps the argument in torch.Tensor(...), which raises for its own float default 1.0 - callers pass the
+        #  int 1, jointopt.py:118; any real number is accepted here)
+        int_scales_object=const((1,), int_scale_init), int_scale_object_mean=const((1,), 1), int_scale_hand_mean=const((1,), 1),
+        ref_mask_object=(tmo > 0).float(), keep_mask_object=(tmo >= 0).float(), ref_mask_hand=(tmh > 0).float(),
+        keep_mask_hand=(tmh >= 0).float(), camintr_rois_object=f32(camintr_rois_object),
+        camintr_rois_hand=f32(camintr_rois_hand), camintr=camintr.contiguous())
+    if masks_hand is not None:
+        out["masks_human"] = torch.as_tensor(masks_hand).detach()
+    out["masks_object"] = masks_object.unsqueeze(0) if masks_object.dim() == 2 else masks_object
+    return out
+
+
 class HOMan(nn.Module):
     def __init__(self, translations_object, rotations_object, verts_object_og, faces_object, translations_hand,
                  rotations_hand, verts_hand_og, ref_verts2d_hand, hand_sides, mano_trans, mano_rot, mano_betas,
@@ -75,30 +121,7 @@ class HOMan(nn.Module):
         if not torch.cuda.is_available():
             raise RuntimeError("homan_amd.HOMan needs an MI355X (ROCm) device; there is no CPU path")
         dev = torch.device("cuda")
-        f32 = lambda t: t.detach().clone().float()
-
-        self.translations_object = nn.Parameter(f32(translations_object), requires_grad=True)
         self.hand_proj_mode = hand_proj_mode
-        rotations_object = f32(rotations_object)
-        rot6d_o = matrix_to_rot6d(rotations_object) if rotations_object.shape[-1] == 3 else rotations_object
-        self.rotations_object = nn.Parameter(rot6d_o.detach().clone().contiguous(), requires_grad=True)
-        self.register_buffer("verts_object_og", f32(verts_object_og))
-
-        self.translations_hand = nn.Parameter(f32(translations_hand), requires_grad=True)
-        rotations_hand = f32(rotations_hand)
-        if rotations_hand.shape[-1] == 3:
-            rotations_hand = matrix_to_rot6d(rotations_hand)
-        self.rotations_hand = nn.Parameter(rotations_hand.detach().clone().contiguous(), requires_grad=True)
-        if cams_hand is None:
-            if hand_proj_mode == "ortho":      # (checked here, on the host input: forward may run inside a stream capture)
-                raise ValueError("hand_proj_mode='ortho' needs cams_hand (scaled-orthographic [s, tx, ty] per hand, s != 0)")
-            cams_hand = torch.zeros(translations_hand.shape[0], 3)
-        elif hand_proj_mode == "ortho" and bool((torch.as_tensor(cams_hand).detach().reshape(-1, 3)[:, 0] == 0).any()):
-            raise ValueError("hand_proj_mode='ortho': cams_hand holds a zero scale (the translation is f / s)")
-        if optimize_ortho_cam:
-            self.cams_hand = nn.Parameter(f32(cams_hand), requires_grad=True)
-        else:
-            self.register_buffer("cams_hand", f32(cams_hand))
         self.hand_sides = hand_sides
         self.hand_nb = len(hand_sides)
         for side in hand_sides:
@@ -106,61 +129,30 @@ class HOMan(nn.Module):
                 raise ValueError(f"{side} not in [left|right]")           # reference manomodel.py:141
         if self.hand_nb not in (1, 2):      # the reference's collision term de-interleaves with a stride of 2 (lossutils.py:58)
             raise NotImplementedError("one or two hands per frame; got %d" % self.hand_nb)
-
-        self.optimize_mano = optimize_mano
-        if optimize_mano:
-            self.mano_pca_pose = nn.Parameter(f32(mano_pca_pose), requires_grad=True)
-            self.mano_rot = nn.Parameter(f32(mano_rot), requires_grad=True)
-            self.mano_trans = nn.Parameter(f32(mano_trans), requires_grad=True)
-        else:   # reference homan.py:104-106: no mano_trans at all in this mode
-            self.register_buffer("mano_pca_pose", f32(mano_pca_pose))
-            self.register_buffer("mano_rot", f32(mano_rot))
-        if optimize_mano_beta:
-            self.mano_betas = nn.Parameter(torch.zeros_like(f32(mano_betas)), requires_grad=True)
-            self.register_buffer("int_scales_hand", torch.ones(1).float() * int_scale_init)
-        else:
-            self.register_buffer("mano_betas", torch.zeros_like(f32(mano_betas)))
-            self.int_scales_hand = nn.Parameter(int_scale_init * torch.ones(1).float(), requires_grad=True)
-        self.register_buffer("verts_hand_og", f32(verts_hand_og))
-        self.register_buffer("ref_verts2d_hand", f32(ref_verts2d_hand))
-
-        # (reference homan.py:122 wraps the argument in torch.Tensor(...), which raises for its own float default 1.0 -
-        #  callers pass the int 1, jointopt.py:118; any real number is accepted here)
-        init_scales = float(int_scale_init) * torch.ones(1).float()
-        self.optimize_object_scale = optimize_object_scale
-        if optimize_object_scale:
-            self.int_scales_object = nn.Parameter(init_scales, requires_grad=True)
-        else:
-            self.register_buffer("int_scales_object", init_scales)
-        self.register_buffer("int_scale_object_mean", torch.ones(1).float())
-        self.register_buffer("int_scale_hand_mean", torch.ones(1).float())
-        self.register_buffer("ref_mask_object", (target_masks_object > 0).float())
-        self.register_buffer("keep_mask_object", (target_masks_object >= 0).float())
-        self.register_buffer("ref_mask_hand", (target_masks_hand > 0).float())
-        self.register_buffer("keep_mask_hand", (target_masks_hand >= 0).float())
-        self.register_buffer("camintr_rois_object", f32(camintr_rois_object))
-        self.register_buffer("camintr_rois_hand", f32(camintr_rois_hand))
-        self.register_buffer("faces_object", faces_object.detach().clone())
-        # white per-face textures of the single-mesh depth renders (reference homan.py:145-151; state_dict keys)
-        self.register_buffer("textures_object", torch.ones(faces_object.shape[0], faces_object.shape[1], 1, 1, 1, 3))
-        self.register_buffer("textures_hand", torch.ones(faces_hand.shape[0], faces_hand.shape[1], 1, 1, 1, 3))
-        self.register_buffer("faces_hand", faces_hand.detach().clone())
-        if camintr is None:
-            camintr = torch.tensor([[[1, 0, 0.5], [0, 1, 0.5], [0, 0, 1]]], dtype=torch.float32)
-        else:
-            camintr = torch.as_tensor(camintr).float()
-            if camintr.dim() == 2:
-                camintr = camintr.unsqueeze(0)
+        self.optimize_mano, self.optimize_object_scale = optimize_mano, optimize_object_scale
+        # everything clip-dependent, from the one preprocessing (clip_tensors); the options decide Parameter or buffer
+        free = {"translations_object", "rotations_object", "translations_hand", "rotations_hand"}
+        free |= {"cams_hand"} if optimize_ortho_cam else set()
+        free |= {"mano_pca_pose", "mano_rot", "mano_trans"} if optimize_mano else set()
+        free |= {"mano_betas"} if optimize_mano_beta else {"int_scales_hand"}
+        free |= {"int_scales_object"} if optimize_object_scale else set()
+        for name, t in clip_tensors(translations_object, rotations_object, verts_object_og, translations_hand, rotations_hand,
+                                    verts_hand_og, ref_verts2d_hand, mano_trans, mano_rot, mano_betas, mano_pca_pose,
+                                    masks_object, masks_hand, camintr_rois_object, camintr_rois_hand, target_masks_object,
+                                    target_masks_hand, cams_hand, camintr, int_scale_init, hand_proj_mode).items():
+            if name == "camintr":       # (the topology's place in the reference's registration order, homan.py:144-151)
+                self.register_buffer("faces_object", faces_object.detach().clone())
+                # white per-face textures of the single-mesh depth renders (state_dict keys)
+                self.register_buffer("textures_object", torch.ones(faces_object.shape[0], faces_object.shape[1], 1, 1, 1, 3))
+                self.register_buffer("textures_hand", torch.ones(faces_hand.shape[0], faces_hand.shape[1], 1, 1, 1, 3))
+                self.register_buffer("faces_hand", faces_hand.detach().clone())
+            t = torch.empty_like(t, device=dev).copy_(t)      # (the model's own storage, wherever the caller's tensor lives)
+            if name in free:
+                setattr(self, name, nn.Parameter(t, requires_grad=True))
+            elif name != "mano_trans":   # reference homan.py:104-106: no mano_trans at all without optimize_mano
+                self.register_buffer(name, t)
         batch = translations_object.shape[0]
-        if camintr.shape[0] == 1 and batch > 1:
-            camintr = camintr.repeat(batch, 1, 1)
-        self.register_buffer("camintr", camintr.contiguous())
         self.image_size = image_size
-        if masks_hand is not None:
-            self.register_buffer("masks_human", masks_hand.detach().clone())
-        if masks_object.dim() == 2:
-            masks_object = masks_object.unsqueeze(0)
-        self.register_buffer("masks_object", masks_object.detach().clone())
         self.cuda()
 
         # leaves: MANO layer (kept out of saved checkpoints by its "mano_model" prefix, fit_vid_dataset.py:366-371)
@@ -209,88 +201,44 @@ class HOMan(nn.Module):
             raise NotImplementedError(f"ordinal depth term: image_size {image_size} > 1024 (rendered at image_size; scale the "
                                       "instance masks and intrinsics down, or leave ordinal_depth off)")
         self._depth_state = None
-        self._depth_state_hands = None
         with torch.no_grad():
             self.verts_hand_init = self.get_verts_hand()[0].detach().clone()
             self.verts_object_init = self.get_verts_object()[0].detach().clone()
         self._setup_visualisation(batch)
 
     # ------------------------------------------------------------------ another clip into the same model
-    def load_clip(self, translations_object, rotations_object, verts_object_og, translations_hand, rotations_hand,
-                  verts_hand_og, ref_verts2d_hand, mano_trans, mano_rot, mano_betas, mano_pca_pose, masks_object, masks_hand,
-                  camintr_rois_object, camintr_rois_hand, target_masks_object, target_masks_hand, cams_hand=None,
-                  camintr=None, int_scale_init=1.0, faces_object=None, faces_hand=None, hand_sides=None, **_same):
-        """The data arguments of the constructor (reference homan/homan.py:27-60) for ANOTHER clip of the same shapes, copied
-        IN PLACE into this model's Parameters and buffers: every context, workspace and captured graph built on them stays
-        valid (a resident stepper fits a stream of clips without rebuilding anything, jointopt.ClipFitter).  Same
-        preprocessing as __init__: rotation matrices -> 6-D, betas start at zero (:108), scales at `int_scale_init`,
-        target masks -> ref / keep (:131-134).  Topologies and hand sides are the model's own (checked when given)."""
-        f32 = lambda t: torch.as_tensor(t).detach().float()
-
-        def put(dst, src):
-            src = f32(src)
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"load_clip: shape {tuple(src.shape)} does not fit the model's {tuple(dst.shape)}")
-            dst.data.copy_(src, non_blocking=True)
-
-        def rot6d(r):
-            r = f32(r)
-            return matrix_to_rot6d(r) if r.shape[-1] == 3 else r
-
+    def load_clip(self, faces_object=None, hand_sides=None, **clip):
+        """The data arguments of the constructor (reference homan/homan.py:27-60) for ANOTHER clip of the same shapes, through
+        the constructor's preprocessing (clip_tensors), copied IN PLACE into this model's Parameters and buffers: every context,
+        workspace and captured graph built on them stays valid (a resident stepper fits a stream of clips without rebuilding
+        anything, jointopt.ClipFitter).  Topologies and hand sides are the model's own (checked when given).  Every check comes
+        before the first copy: a clip that is refused leaves the model as it was."""
         if hand_sides is not None and list(hand_sides) != list(self.hand_sides):
             raise ValueError("load_clip: other hand sides")
         if faces_object is not None and not torch.equal(torch.as_tensor(faces_object)[0].cpu(), self.faces_object[0].cpu()):
             raise ValueError("load_clip: other object topology")
+        new = clip_tensors(**dict(clip, hand_proj_mode=self.hand_proj_mode, device=self.translations_object.device))
+        pairs = [(name, getattr(self, name), src) for name, src in new.items() if hasattr(self, name)]
+        for name, dst, src in pairs:
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"load_clip: {name} of shape {tuple(src.shape)} does not fit the model's {tuple(dst.shape)}")
         with torch.no_grad():
-            put(self.translations_object, translations_object)
-            put(self.rotations_object, rot6d(rotations_object))
-            put(self.verts_object_og, verts_object_og)
-            put(self.translations_hand, translations_hand)
-            put(self.rotations_hand, rot6d(rotations_hand))
-            put(self.cams_hand, cams_hand if cams_hand is not None else torch.zeros_like(self.cams_hand))
-            put(self.mano_pca_pose, mano_pca_pose)
-            put(self.mano_rot, mano_rot)
-            if self.optimize_mano:
-                put(self.mano_trans, mano_trans)
-            self.mano_betas.data.zero_()
-            self.int_scales_hand.data.fill_(float(int_scale_init))
-            self.int_scales_object.data.fill_(float(int_scale_init))
-            put(self.verts_hand_og, verts_hand_og)
-            put(self.ref_verts2d_hand, ref_verts2d_hand)
-            tmo = f32(target_masks_object).to(self.ref_mask_object.device, non_blocking=True)
-            tmh = f32(target_masks_hand).to(self.ref_mask_hand.device, non_blocking=True)
-            put(self.ref_mask_object, tmo > 0)
-            put(self.keep_mask_object, tmo >= 0)
-            put(self.ref_mask_hand, tmh > 0)
-            put(self.keep_mask_hand, tmh >= 0)
-            put(self.camintr_rois_object, camintr_rois_object)
-            put(self.camintr_rois_hand, camintr_rois_hand)
-            # (no intrinsics = the constructor's default, homan.py:113-116 - NOT the previous clip's: a clip loaded into a
-            #  resident model must fit exactly like a freshly built one)
-            c = (torch.tensor([[[1, 0, 0.5], [0, 1, 0.5], [0, 0, 1]]], dtype=torch.float32) if camintr is None
-                 else torch.as_tensor(camintr).float())
-            c = c.unsqueeze(0) if c.dim() == 2 else c
-            put(self.camintr, c.expand_as(self.camintr) if c.shape[0] == 1 else c)
-            self.losses.camintr.copy_(self.camintr)
-            if masks_hand is not None and hasattr(self, "masks_human"):
-                self.masks_human.copy_(torch.as_tensor(masks_hand).to(self.masks_human.dtype))
-            mo = torch.as_tensor(masks_object)
-            self.masks_object.copy_((mo.unsqueeze(0) if mo.dim() == 2 else mo).to(self.masks_object.dtype))
-            self.losses.keep_sum.copy_(self.keep_mask_object.sum().reshape(1))
-            self.losses.sil_ctx.invalidate_outputs()
-            self._mano_cache = None
-            if self._depth_state is not None:
-                ctx_o, ctx_h, m_o, m_h = self._depth_state
-                m_o.copy_((self.masks_object != 0).to(torch.uint8))
-                m_h.copy_((self.masks_human != 0).to(torch.uint8))
-            if getattr(self, "_depth_state_hands", None) is not None:
-                _, _, m_o, m_hs = self._depth_state_hands
-                m_o.copy_((self.masks_object != 0).to(torch.uint8))
-                for h, m in enumerate(m_hs):
-                    m.copy_((self.masks_human[h::self.hand_nb] != 0).to(torch.uint8))
-            self.verts_hand_init.copy_(self.get_verts_hand()[0].detach())
-            self.verts_object_init.copy_(self.get_verts_object()[0].detach())
-            self._mano_cache = None
+            for name, dst, src in pairs:     # (the instance masks come in the caller's dtype and are converted on the way)
+                dst.data.copy_(src, non_blocking=not name.startswith("masks_"))
+            self._refresh_derived()
+
+    def _refresh_derived(self):
+        """Everything in the model that FOLLOWS its clip-dependent Parameters and buffers, brought up to them - the complete
+        list (anything new that is computed from a clip's data and kept belongs here)."""
+        self.losses.keep_sum.copy_(self.keep_mask_object.sum().reshape(1))
+        self.losses.sil_ctx.invalidate_outputs()         # the raster's region state: outputs it skipped as unchanged
+        if self._depth_state is not None:
+            for dst, src in zip(self._depth_state[1], self._depth_masks()):
+                dst.copy_(src)
+        self._mano_cache = None
+        self.verts_hand_init.copy_(self.get_verts_hand()[0].detach())
+        self.verts_object_init.copy_(self.get_verts_object()[0].detach())
+        self.renderer.K.copy_(self.camintr)
 
     # ------------------------------------------------------------------ visualisation (reference homan.py:168-219, 510-628)
     def _setup_visualisation(self, batch_size):
@@ -445,36 +393,30 @@ class HOMan(nn.Module):
                                        self.int_scales_hand, abs_scale=False)
 
     # ------------------------------------------------------------------ losses
-    def depth_contexts(self):
-        """(object raster context, hand raster context, object instance mask u8, hand instance mask u8) of the ordinal depth
-        term, at the full-image size (built once)."""
+    def _depth_masks(self):
+        """the u8 instance masks of the ordinal depth term's layers [object, hand 0, (hand 1)], from the model's buffers"""
+        size = int(self.image_size)
+        if tuple(self.masks_object.shape[1:]) != (size, size) or tuple(self.masks_human.shape[1:]) != (size, size):
+            raise NotImplementedError("ordinal depth: instance masks must be (B, image_size, image_size), got "
+                                      f"{tuple(self.masks_object.shape)} / image_size {size}")
+        return [(m != 0).to(torch.uint8).contiguous()
+                for m in [self.masks_object] + [self.masks_human[h::self.hand_nb] for h in range(self.hand_nb)]]
+
+    def depth_layers(self):
+        """([raster context], [instance mask u8]) of the ordinal depth term, one of each per layer [object, hand 0, (hand 1)], at
+        the full-image size (built once) - a context carries ONE render's intermediates to its backward, so every layer has its own"""
         if self._depth_state is None:
-            size = int(self.image_size)
-            masks_o, masks_h = self.masks_object, self.masks_human
-            if tuple(masks_o.shape[1:]) != (size, size) or tuple(masks_h.shape[1:]) != (size, size):
-                raise NotImplementedError("ordinal depth: instance masks must be (B, image_size, image_size), got "
-                                          f"{tuple(masks_o.shape)} / image_size {size}")
+            masks = self._depth_masks()
             batch, dev = self.translations_object.shape[0], self.translations_object.device
-            ctx_o = ops.SilhouetteContext(self.faces_object, self.verts_object_og.shape[1], batch, size, dev)
-            ctx_h = ops.SilhouetteContext(self.faces_hand[:1].expand(batch, -1, -1), 778, batch, size, dev)
-            self._depth_state = (ctx_o, ctx_h, (masks_o != 0).to(torch.uint8).contiguous(),
-                                 (masks_h != 0).to(torch.uint8).contiguous())
+            faces = [self.faces_object] + [self.faces_hand[h:h + 1].expand(batch, -1, -1) for h in range(self.hand_nb)]
+            self._depth_state = ([ops.SilhouetteContext(f, m.shape[1], batch, int(self.image_size), dev)
+                                  for f, m in zip(faces, [self.verts_object_og] + [self.verts_hand_og] * self.hand_nb)], masks)
         return self._depth_state
 
-    def _depth_contexts_hands(self):
-        """two hands per frame: (object context, [one raster context per hand], object mask u8, [per-hand masks u8]) - a context
-        carries ONE render's intermediates to its backward, so every layer has its own"""
-        if getattr(self, "_depth_state_hands", None) is None:
-            size = int(self.image_size)
-            if tuple(self.masks_object.shape[1:]) != (size, size) or tuple(self.masks_human.shape[1:]) != (size, size):
-                raise NotImplementedError("ordinal depth: instance masks must be (B, image_size, image_size)")
-            batch, dev = self.translations_object.shape[0], self.translations_object.device
-            ctx_o = ops.SilhouetteContext(self.faces_object, self.verts_object_og.shape[1], batch, size, dev)
-            ctx_hs = [ops.SilhouetteContext(self.faces_hand[h:h + 1].expand(batch, -1, -1), 778, batch, size, dev)
-                      for h in range(self.hand_nb)]
-            m_hs = [(self.masks_human[h::self.hand_nb] != 0).to(torch.uint8).contiguous() for h in range(self.hand_nb)]
-            self._depth_state_hands = (ctx_o, ctx_hs, (self.masks_object != 0).to(torch.uint8).contiguous(), m_hs)
-        return self._depth_state_hands
+    def depth_contexts(self):
+        """the one-hand view of depth_layers(): (object context, hand context, object mask u8, hand mask u8)"""
+        ctxs, masks = self.depth_layers()
+        return ctxs[0], ctxs[1], masks[0], masks[1]
 
     def compute_ordinal_depth_loss(self, verts_object=None, verts_hand=None):
         """reference homan/homan.py:384-419: render object and hand depth at the full-image intrinsics, compare their
@@ -485,14 +427,13 @@ class HOMan(nn.Module):
             verts_hand, _ = self.get_verts_hand()
         if self.hand_nb != 1:
             # layers [object, hand 0, hand 1] (homan.py:403-417: one render per hand over its strided rows), every pair of them
-            ctx_o, ctx_hs, m_o, m_hs = self._depth_contexts_hands()
+            ctxs, masks = self.depth_layers()
             sils, deps = [], []
-            for verts, ctx in [(verts_object, ctx_o)] + [(verts_hand[h::self.hand_nb].contiguous(), ctx_hs[h])
-                                                         for h in range(self.hand_nb)]:
+            for verts, ctx in zip([verts_object] + [verts_hand[h::self.hand_nb].contiguous() for h in range(self.hand_nb)], ctxs):
                 sil, dep = ops.depth_render(verts, self.camintr, ctx, 1.0)
                 sils.append(sil)
                 deps.append(dep)
-            return {"loss_depth": ops.ordinal_depth_loss_layers(deps, sils, [m_o] + m_hs, self.reduce_ws)}
+            return {"loss_depth": ops.ordinal_depth_loss_layers(deps, sils, masks, self.reduce_ws)}
         ctx_o, ctx_h, m_o, m_h = self.depth_contexts()
         sil_o, dep_o = ops.depth_render(verts_object, self.camintr, ctx_o, 1.0)
         sil_h, dep_h = ops.depth_render(verts_hand, self.camintr, ctx_h, 1.0)

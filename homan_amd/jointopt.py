@@ -86,10 +86,7 @@ class GraphStepper:
         gradients, log -, the captured graph reused as it is."""
         with torch.no_grad():
             self.model.load_clip(**clip_inputs)
-            for st_m, st_v in self.opt.state:
-                st_m.zero_()
-                st_v.zero_()
-            self.opt.step_t.zero_()
+            self.opt.reset()
             self.log.buf.zero_()
             for p in self.model.parameters():
                 if p.grad is not None:

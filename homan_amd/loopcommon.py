@@ -82,6 +82,13 @@ class HmAdam:
         self.grads = [p.grad for p, _ in self.items]       # keep the static buffers alive
         self.blocks = max(1, min(64, (max(p.numel() for p, _ in self.items) + 255) // 256))
 
+    def reset(self):
+        """back to before the first step (another fit on the same buffers): moments and step counter zeroed"""
+        for st_m, st_v in self.state:
+            st_m.zero_()
+            st_v.zero_()
+        self.step_t.zero_()
+
     def step(self, zero_grad=True, log=None):
         """log = (vals (C, n+1), weights (n), n, max_steps, log_buf, C): the log row of the step being taken is written by the
         same launch (hm_adam_step_log = hm_log_total_clips + hm_adam_step)."""

@@ -16,7 +16,7 @@ class Losses:
         self.ref_mask_hand, self.keep_mask_hand = ref_mask_hand, keep_mask_hand
         self.ref_verts2d_hand = ref_verts2d_hand
         self.camintr_rois_object, self.camintr_rois_hand = camintr_rois_object, camintr_rois_hand
-        self.camintr = camintr.clone()
+        self.camintr = camintr      # (the model's buffer, like the masks: a clip loaded into the model is seen here)
         self.thresh = constants.INTERACTION_Z_THRESH
         self.expansion = constants.INTERACTION_BBOX_EXPANSION
         self.class_name, self.hand_nb = class_name, hand_nb

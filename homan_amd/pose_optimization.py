@@ -503,10 +503,7 @@ class _FusedPoseLoop:
         for dst, src in pairs:
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
-        for mm, vv in self.opt.state:
-            mm.zero_()
-            vv.zero_()
-        self.opt.step_t.zero_()
+        self.opt.reset()
         for p in self.params:
             p.grad.zero_()
         self.best_loss.fill_(float("inf"))

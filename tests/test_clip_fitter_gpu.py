@@ -38,19 +38,21 @@ def _same(result, model, evo):
 
 
 @pytest.mark.parametrize("step2", [False, True])
-def test_reloaded_stepper_equals_fresh_fits(step2, mano_model):
+@pytest.mark.parametrize("size", [64, 80])      # 80: off the raster's tile grid, rendered padded to 96 - the stepper's own padded masks / K
+def test_reloaded_stepper_equals_fresh_fits(size, step2, mano_model):
     from homan_amd import lib, synth
     from homan_amd.jointopt import ClipFitter
     lw = dict(synth.STEP2_LOSS_WEIGHTS if step2 else synth.STEP1_LOSS_WEIGHTS)
-    clips = [_clip(mano_model, s) for s in (11, 12, 13)]
-    fitter = ClipFitter(lw, num_iterations=STEPS, optimize_mano=True, image_size=64, mano_model=mano_model, rend_size=64)
+    clips = [_clip(mano_model, s, size=size) for s in (11, 12, 13)]
+    fitter = ClipFitter(lw, num_iterations=STEPS, optimize_mano=True, image_size=size, mano_model=mano_model, rend_size=size)
     graphs0 = len(lib._KEPT_GRAPHS)
     results = fitter.fit(clips)
     assert fitter.timing["built"] == 1 and fitter.timing["reused"] == 2
     # one resident stepper for the three clips: its one-iteration graph and its K-iterations-per-replay twin, nothing per clip
     assert len(lib._KEPT_GRAPHS) - graphs0 == 2
+    assert fitter.resident[next(iter(fitter.resident))].model.sil_ctx.padded == (size == 80)
     for clip, res in zip(clips, results):
-        model, evo = _fresh(mano_model, clip, lw)
+        model, evo = _fresh(mano_model, clip, lw, size)
         _same(res, model, evo)
 
 
@@ -109,10 +111,11 @@ def test_clip_without_intrinsics_and_one_at_a_time_configurations(mano_model):
         _same(r, *_fresh(mano_model, clip, lw))
 
 
-def test_depth_term_in_resident_clip_batches(mano_model):
-    """The ordinal depth term (opt-in, reference homan.py:384-419) through ClipFitter with two clips per batch: the second
-    batch is COPIED into the resident stepper - its instance masks included (round 5: a resident batch used to refuse the
-    reload and the fitter fell back to one clip per stepper) - and every clip equals its fresh solo fit bit for bit."""
+@pytest.mark.parametrize("clips_per_batch", [1, 2])
+def test_depth_term_in_resident_clip_batches(clips_per_batch, mano_model):
+    """The ordinal depth term (opt-in, reference homan.py:384-419) through ClipFitter with one and two clips per batch: the
+    following batches are COPIED into the resident stepper - their instance masks included (round 5: a resident batch used to
+    refuse the reload and the fitter fell back to one clip per stepper) - and every clip equals its fresh solo fit bit for bit."""
     from homan_amd import synth
     from homan_amd.jointopt import ClipFitter, optimize_hand_object
     lw = dict(synth.STEP1_LOSS_WEIGHTS, lw_depth=1.0)
@@ -124,10 +127,10 @@ def test_depth_term_in_resident_clip_batches(mano_model):
             pp["masks"] = torch.zeros_like(pp["masks"])
             pp["translations"] = pp["translations"] + torch.tensor([0.06, 0.0, -0.02])
         clips.append(clip)
-    fitter = ClipFitter(lw, num_iterations=STEPS, clips_per_batch=2, optimize_mano=True, image_size=64, mano_model=mano_model,
-                        rend_size=64, ordinal_depth=True)
+    fitter = ClipFitter(lw, num_iterations=STEPS, clips_per_batch=clips_per_batch, optimize_mano=True, image_size=64,
+                        mano_model=mano_model, rend_size=64, ordinal_depth=True)
     res = fitter.fit(clips)
-    assert fitter.timing["built"] == 1 and fitter.timing["reused"] == 1
+    assert fitter.timing["built"] == 1 and fitter.timing["reused"] == len(clips) // clips_per_batch - 1
     for clip, r in zip(clips, res):
         model, evo, _ = optimize_hand_object(copy.deepcopy(clip["person_parameters"]), copy.deepcopy(clip["object_parameters"]),
                                              objvertices=clip["objvertices"], objfaces=clip["objfaces"], camintr=clip["camintr"],
@@ -135,3 +138,27 @@ def test_depth_term_in_resident_clip_batches(mano_model):
                                              mano_model=mano_model, rend_size=64, ordinal_depth=True)
         assert evo["loss_depth"][0] > 0
         _same(r, model, evo)
+
+
+def test_load_clip_refreshes_what_follows_the_buffers(mano_model):
+    """clip B, with other intrinsics, loaded into a model built from clip A: everything the model derives from a clip's data
+    and keeps equals what a model built from B holds"""
+    from homan_amd.jointopt import build_model, collate_inputs
+    a, b = _clip(mano_model, 61), _clip(mano_model, 62)
+    b = dict(b, camintr=b["camintr"] * np.array([[1.1], [0.9], [1.0]], np.float32))
+    build = lambda c: build_model(copy.deepcopy(c["person_parameters"]), copy.deepcopy(c["object_parameters"]),
+                                  objvertices=c["objvertices"], objfaces=c["objfaces"], camintr=c["camintr"], optimize_mano=True,
+                                  image_size=64, mano_model=mano_model, rend_size=64)
+    model, fresh = build(a), build(b)
+    assert not torch.equal(model.renderer.K, fresh.renderer.K) and not torch.equal(model.masks_object, fresh.masks_object)
+    depth = model.depth_contexts()          # (built BEFORE the load: its masks must follow)
+    model.load_clip(camintr=b["camintr"], **collate_inputs(b["person_parameters"], b["object_parameters"], b["objvertices"],
+                                                           b["objfaces"]))
+    assert torch.equal(model.renderer.K, model.camintr) and torch.equal(model.renderer.K, fresh.renderer.K)
+    assert torch.equal(model.losses.camintr, fresh.camintr)
+    assert torch.equal(model.losses.keep_sum, fresh.losses.keep_sum)
+    assert torch.equal(model.verts_object_init, fresh.verts_object_init)
+    assert torch.equal(model.verts_hand_init, fresh.verts_hand_init)
+    for got, want in zip(depth[2:], fresh.depth_contexts()[2:]):
+        assert got.dtype == torch.uint8 and torch.equal(got, want)
+    assert all(x is y for x, y in zip(depth, model.depth_contexts()))

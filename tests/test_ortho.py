@@ -140,3 +140,13 @@ def test_clip_fitter_takes_ortho_clips_through_the_graph_loop(mano_model):
         np.testing.assert_array_equal(res["loss_evolution"]["loss"], evo["loss"])
         assert torch.equal(res["state_dict"]["cams_hand"], model.cams_hand.detach().cpu())
         assert torch.equal(res["verts_hand"], model.get_verts_hand()[0].detach().cpu())
+    # a clip the constructor refuses (a zero camera scale: the translation is f / s) behind a good clip of its shape: the
+    # resident model refuses it like a fresh one - not f / 0 inside the captured graph - and stays as it was
+    bad = copy.deepcopy(clips[0])
+    bad["person_parameters"][1]["cams"] = bad["person_parameters"][1]["cams"] * torch.tensor([0.0, 1.0, 1.0])
+    resident = [st.model for st in fitter.resident_graph.values() if st.model.translations_object.shape[0] == 4][0]
+    before = {k: p.detach().clone() for k, p in resident.named_parameters()}
+    with pytest.raises(ValueError, match="zero scale"):
+        fitter.fit([bad])
+    for k, p in resident.named_parameters():
+        assert torch.equal(p.detach(), before[k]), k
