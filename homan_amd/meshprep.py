@@ -9,6 +9,10 @@ sign field and surface nets on it (`ops.surface_nets`, csrc/remesh.hip), and a s
 closed and oriented by construction; it is not feature preserving (no sharp edges), decimates only through the lattice pitch,
 loses components thinner than a cell, and may hold pinched vertices.
 
+Opt-in second stage, for sources with parts thinner than a cell of the budget lattice: `make_watertight_detail` meshes at a fine
+lattice and `decimate` brings the nets down to the budget by quadric edge collapses in deterministic parallel rounds
+(`ops.decimate_mesh`, csrc/decimate.hip); `simplify_mesh(..., detail_resolution=R)` selects it.
+
 Also here: a minimal reader and writer for .obj and .off files in plain Python and NumPy."""
 import os
 import pickle
@@ -193,15 +197,65 @@ def make_watertight(vertices, faces, resolution=None, target_vertices=1000, snap
             "source_topology": meshutils.mesh_topology(f), "topology": meshutils.mesh_topology(out_f) if len(out_f) else None}
 
 
+def _check_decimation(target_vertices, regularity, max_rounds):
+    from . import ops
+    return ops._decimate_numbers(target_vertices, regularity, max_rounds)
+
+
+def decimate(vertices, faces, target_vertices=1000, regularity=0.01, max_rounds=4096):
+    """A closed, oriented mesh brought down to target_vertices by quadric edge collapses in deterministic parallel rounds
+    (`ops.decimate_mesh`, csrc/decimate.hip; the rules in include/homan_amd.h and DESIGN.md section 7) -> {"vertices" (n,3)
+    float32, "faces" (m,3) int64 (NumPy, on the host), "rounds", "reached" (n <= target_vertices; False when the rounds got stuck
+    or ran out), "collapses" per round, "topology"}.  The input must be closed and oriented, no face may repeat a vertex, indices
+    in range, coordinates finite: checked on the host before any device work (`ops.closed_mesh`, ValueError); vertices that no
+    face names are dropped there, the others keep their order.
+    regularity >= 0 weighs the cube of the squared edge length against the quadric error: in flat regions it sends the shortest
+    edge first.  The work is HIP (no CPU path)."""
+    from . import meshutils, ops
+    target_vertices, regularity, max_rounds = _check_decimation(target_vertices, regularity, max_rounds)
+    out = ops.decimate_mesh(vertices, faces, target_vertices, regularity, max_rounds)
+    out_f = out["faces"].cpu().numpy().astype(np.int64)
+    return {"vertices": out["vertices"].cpu().numpy(), "faces": out_f, "rounds": out["rounds"], "reached": out["reached"],
+            "collapses": out["collapses"], "topology": meshutils.mesh_topology(out_f)}
+
+
+def make_watertight_detail(vertices, faces, detail_resolution, target_vertices=1000, snap_limit=SNAP_LIMIT, sign="winding",
+                           regularity=0.01, max_rounds=4096):
+    """The two-stage preparation: `make_watertight` at the FINE lattice detail_resolution (2 ... 256, no budget search), its snap,
+    then `decimate` down to target_vertices -> `make_watertight`'s dict ("probes" is None; "vertices", "faces", "topology" are
+    the decimated mesh's) with "detail_vertices" (the nets' vertex count), "rounds", "reached" and "collapses" added.  Nets that
+    already meet the budget come back unchanged with rounds = 0.  Where the budget lattice loses parts thinner than its cell (a
+    mug's wall and handle), the fine lattice keeps them and the collapses keep the topology.  Arguments are checked before any
+    device work; the work is HIP (no CPU path)."""
+    from . import meshutils, ops
+    target_vertices, regularity, max_rounds = _check_decimation(target_vertices, regularity, max_rounds)
+    if detail_resolution is None or isinstance(detail_resolution, bool):
+        raise ValueError(f"detail_resolution {detail_resolution!r} is not an integer in [{ops.LATTICE_RESOLUTIONS[0]}, "
+                         f"{ops.LATTICE_RESOLUTIONS[1]}]")
+    out = make_watertight(vertices, faces, resolution=detail_resolution, snap_limit=snap_limit, sign=sign)
+    out.update(detail_vertices=len(out["vertices"]), rounds=0, reached=len(out["vertices"]) <= target_vertices, collapses=[])
+    if not out["reached"]:
+        small = ops.decimate_mesh(out["vertices"], out["faces"], target_vertices, regularity, max_rounds)
+        out_f = small["faces"].cpu().numpy().astype(np.int64)
+        out.update(vertices=small["vertices"].cpu().numpy(), faces=out_f, rounds=small["rounds"], reached=small["reached"],
+                   collapses=small["collapses"], topology=meshutils.mesh_topology(out_f))
+    return out
+
+
 def simplify_mesh(src_path, target_path, vert_nb=1000, save_pkl=True, **ignored):
     """The reference's meshprocess/simplifymesh.py simplify_mesh: reads src_path (.obj / .off), writes target_path (.obj / .off)
     with at most vert_nb vertices, watertight, and with save_pkl the pickle {"vertices", "faces"} next to it (the target's name
     with its extension replaced by .pkl) -> `make_watertight`'s dict.  manifold_path, acvd_path, tmp_folder and the like are accepted
-    and unused: no external program runs."""
+    and unused: no external program runs.  The one keyword that is read: detail_resolution (default None = the budget lattice);
+    an integer selects `make_watertight_detail`, the fine lattice followed by the edge-collapse decimation."""
+    detail_resolution = ignored.get("detail_resolution")
     vertices, faces = load_mesh(src_path)
     if os.path.splitext(target_path)[1].lower() not in (".obj", ".off"):
         raise ValueError(f"{target_path}: only .obj and .off are written")
-    mesh = make_watertight(vertices, faces, target_vertices=vert_nb)
+    if detail_resolution is None:
+        mesh = make_watertight(vertices, faces, target_vertices=vert_nb)
+    else:
+        mesh = make_watertight_detail(vertices, faces, detail_resolution, target_vertices=vert_nb)
     folder = os.path.dirname(os.path.abspath(target_path))
     os.makedirs(folder, exist_ok=True)
     save_mesh(target_path, mesh["vertices"], mesh["faces"])

@@ -1594,3 +1594,165 @@ def lattice_snap(lattice_vertices, closest, d2, pitch, snap_limit):
                                                   _lib.ptr(d2.contiguous()), n, float(sl), float(h), _lib.ptr(out),
                                                   _lib.ptr(snapped), _lib.stream()), "hm_lattice_snap")
     return out, snapped
+
+
+# =============================================================================== edge-collapse decimation (csrc/decimate.hip)
+DECIMATE_MAX_VERTS, DECIMATE_MAX_FACES = 1 << 20, 1 << 22     # DC_MAX_VERTS, DC_MAX_FACES of csrc/decimate.hip
+DECIMATE_RANK_NONE = 2 ** 31 - 1                              # the rank of an invalid edge
+DECIMATE_REGULARITY, DECIMATE_MAX_ROUNDS = 0.01, 4096
+
+
+def closed_mesh(verts, faces):
+    """The input contract of the decimation (include/homan_amd.h), checked on the host -> (verts (n,3) fp32, faces (m,3) int64) as
+    NumPy arrays.  ValueError unless: closed and oriented (`meshutils.mesh_topology`), no face repeats a vertex, every index in
+    range, every coordinate of a vertex that a face names finite, 4 <= n <= 2^20, 4 <= m <= 2^22.  Vertices that no face names
+    (raw scans carry them) are DROPPED here, the others keep their order and the faces are renumbered: the rounds' contract is
+    that every vertex is named."""
+    from . import meshutils
+    v, f = _lattice_mesh(verts, faces)
+    if f.min() < 0 or f.max() >= len(v):
+        raise ValueError(f"faces: an index outside [0, {len(v)})")
+    used = np.unique(f)
+    if len(used) != len(v):
+        v, f = np.ascontiguousarray(v[used]), np.searchsorted(used, f)
+    n, m = len(v), len(f)
+    if not (4 <= n <= DECIMATE_MAX_VERTS and 4 <= m <= DECIMATE_MAX_FACES):
+        raise ValueError(f"a closed mesh of 4 ... 2^20 vertices and 4 ... 2^22 faces is expected, got {n} and {m}")
+    if not np.isfinite(v).all():
+        raise ValueError("verts: a coordinate is not finite")
+    if (f[:, 0] == f[:, 1]).any() or (f[:, 1] == f[:, 2]).any() or (f[:, 2] == f[:, 0]).any():
+        raise ValueError("faces: a face repeats a vertex")
+    topology = meshutils.mesh_topology(f)
+    if not (topology["closed"] and topology["oriented"]):
+        raise ValueError(f"the mesh is not closed and oriented: {topology}")
+    return v, f
+
+
+def _decimate_numbers(target, regularity, max_rounds):
+    for name, x in (("target_vertices", target), ("max_rounds", max_rounds)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError(f"{name} {x!r} is not a positive integer")
+    with np.errstate(over="ignore"):
+        reg = np.float32(regularity) if isinstance(regularity, (int, float, np.floating, np.integer)) and not isinstance(
+            regularity, bool) else np.float32(np.nan)
+    if not (np.isfinite(reg) and reg >= 0):
+        raise ValueError(f"regularity {regularity!r} is not finite and >= 0 in fp32")
+    return int(target), float(reg), int(max_rounds)
+
+
+class _Decimator:
+    """Every buffer of the rounds, sized once from the input (n0 vertices, m0 faces): the library's outputs and the outputs of
+    the sorts, scans and gathers between its entry points, which are torch's (plumbing) and write into these buffers (`out=`).
+    `round` issues one round's launches and makes its one host read.  What torch's sorts and scans need as temporaries of their
+    own comes from its caching allocator."""
+
+    def __init__(self, n0, m0, dev):
+        E0, C0 = 3 * m0 // 2, 3 * m0
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.corner_words = torch.empty(5, C0, dtype=torch.int64, device=dev)     # he, ck, both sorted, the sorts' indices
+        self.edge_words = torch.empty(7, E0, dtype=torch.int64, device=dev)       # keys, orders and what the rank's sorts write
+        self.doubles = torch.empty(10 * n0 + 2 * E0, dtype=torch.float64, device=dev)
+        self.voff, self.corner_ints = torch.empty(n0 + 1, **i32), torch.empty(2, C0, **i32)
+        self.edges, self.per_edge = torch.empty(E0, 4, **i32), torch.empty(6, E0, **i32)
+        self.per_vertex, self.per_face = torch.empty(6, n0, **i32), torch.empty(2, m0, **i32)
+        self.verts = [torch.empty(n0, 3, device=dev) for _ in range(2)]
+        self.faces = [torch.empty(m0, 3, **i32) for _ in range(2)]
+        self.n0, self.m0 = n0, m0
+
+    def round(self, V, F, n, m, need, reg, out_v, out_f):
+        """V (>= n, 3), F (>= m, 3) contiguous device buffers -> (new n, new m, the round's intermediates as views)"""
+        h, p, s = _lib.lib(), _lib.ptr, _lib.stream()
+        E, C = 3 * m // 2, 3 * m
+        E0 = 3 * self.m0 // 2
+        he, ck, he_sorted, corner_sorted, corner_idx = (self.corner_words[k, :C] for k in range(5))
+        cost_keys, l2_keys, by_l2, keys_by_l2, sorted_keys, by_cost, order = (self.edge_words[k, :E] for k in range(7))
+        quadrics = self.doubles[:10 * n]
+        cost, l2 = self.doubles[10 * self.n0:10 * self.n0 + E], self.doubles[10 * self.n0 + E0:10 * self.n0 + E0 + E]
+        voff, edges = self.voff[:n + 1], self.edges[:E]
+        is_edge, edge_scan = self.corner_ints[0, :C], self.corner_ints[1, :C]
+        choice, valid, rank, selected, by_rank, selected_scan = (self.per_edge[k, :E] for k in range(6))
+        m1, m2, remap, vkeep, moved, vertex_scan = (self.per_vertex[k, :n] for k in range(6))
+        fkeep, face_scan = self.per_face[0, :m], self.per_face[1, :m]
+        _lib.check(h.hm_decimate_keys(p(F), n, m, p(he), p(ck), s), "hm_decimate_keys")
+        torch.sort(he, out=(he_sorted, corner_idx))
+        torch.sort(ck, out=(corner_sorted, corner_idx))
+        _lib.check(h.hm_decimate_offsets(p(he_sorted), n, m, p(voff), p(is_edge), s), "hm_decimate_offsets")
+        torch.cumsum(is_edge, 0, dtype=torch.int32, out=edge_scan)
+        _lib.check(h.hm_decimate_costs(p(V), p(F), p(he_sorted), p(corner_sorted), p(voff), p(edge_scan), n, m, reg, p(quadrics),
+                                       p(edges), p(choice), p(cost), p(l2), p(valid), p(cost_keys), p(l2_keys), s),
+                   "hm_decimate_costs")
+        torch.sort(l2_keys, stable=True, out=(sorted_keys, by_l2))
+        torch.index_select(cost_keys, 0, by_l2, out=keys_by_l2)
+        torch.sort(keys_by_l2, stable=True, out=(sorted_keys, by_cost))
+        torch.index_select(by_l2, 0, by_cost, out=order)
+        _lib.check(h.hm_decimate_select(p(edges), p(valid), p(order), p(he_sorted), p(voff), n, m, p(rank), p(m1), p(m2),
+                                        p(selected), p(by_rank), p(remap), p(vkeep), p(moved), s), "hm_decimate_select")
+        torch.cumsum(by_rank, 0, dtype=torch.int32, out=selected_scan)
+        _lib.check(h.hm_decimate_mark(p(F), p(edges), p(rank), p(selected_scan), need, n, m, p(selected), p(remap), p(vkeep),
+                                      p(moved), p(fkeep), s), "hm_decimate_mark")
+        torch.cumsum(vkeep, 0, dtype=torch.int32, out=vertex_scan)
+        torch.cumsum(fkeep, 0, dtype=torch.int32, out=face_scan)
+        _lib.check(h.hm_decimate_compact(p(V), p(F), p(edges), p(choice), p(remap), p(moved), p(vkeep), p(vertex_scan), p(fkeep),
+                                         p(face_scan), n, m, n, m, p(out_v), p(out_f), s), "hm_decimate_compact")
+        new_n = int(vertex_scan[-1])                                       # the round's one host read
+        # two faces go with every collapse (rule 5's link condition); `collapse_round` checks the face scan against it
+        return new_n, m - 2 * (n - new_n), {"edges": edges, "choice": choice, "cost": cost, "l2": l2, "valid": valid, "rank": rank,
+                                            "selected": selected, "vertex_keep": vkeep, "remap": remap, "moved": moved,
+                                            "vertex_scan": vertex_scan, "face_keep": fkeep, "face_scan": face_scan}
+
+
+def _decimate_start(verts, faces, who):
+    v, f = closed_mesh(verts, faces)
+    if not torch.cuda.is_available():
+        raise _lib.HomanAmdError(f"homan_amd.ops.{who} needs the GPU (there is no CPU fallback)")
+    dev = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return v, f, dev
+
+
+def collapse_round(verts, faces, need, regularity=DECIMATE_REGULARITY):
+    """ONE round of the decimation (csrc/decimate.hip, the rules in include/homan_amd.h): verts (n,3), faces (m,3) of a closed,
+    oriented mesh (checked on the host: `closed_mesh`), `need` = the most collapses wanted -> {"vertices" (n',3) fp32, "faces"
+    (m',3) int32 after the round, on the device; the round's intermediates per edge in ascending (a, b): "edges" (E,4) a b c d,
+    "choice" 0 / 1 / 2, "cost", "l2" fp64, "valid", "rank" (2^31 - 1 for an invalid edge), "selected" (after the budget);
+    "collapses"}.  No grad, no CPU path."""
+    if isinstance(need, bool) or not isinstance(need, (int, np.integer)) or need < 0:
+        raise ValueError(f"need {need!r} is not an integer >= 0")
+    _, reg, _ = _decimate_numbers(1, regularity, 1)
+    v, f, dev = _decimate_start(verts, faces, "collapse_round")
+    n, m = len(v), len(f)
+    with torch.cuda.device(dev):
+        work = _Decimator(n, m, dev)
+        work.verts[0].copy_(torch.tensor(v))
+        work.faces[0].copy_(torch.from_numpy(f.astype(np.int32)))
+        new_n, new_m, mid = work.round(work.verts[0], work.faces[0], n, m, int(need), reg, work.verts[1], work.faces[1])
+        kept_faces = int(mid["face_scan"][-1])                             # (a second host read: this entry is the tests')
+    if kept_faces != new_m:
+        raise _lib.HomanAmdError(f"collapse_round: {n - new_n} collapses dropped {m - kept_faces} faces, not two each")
+    out = {k: t.clone() for k, t in mid.items()}
+    out.update(vertices=work.verts[1][:new_n].clone(), faces=work.faces[1][:new_m].clone(), collapses=n - new_n)
+    return out
+
+
+def decimate_mesh(verts, faces, target, regularity=DECIMATE_REGULARITY, max_rounds=DECIMATE_MAX_ROUNDS):
+    """The decimation loop: rounds of `collapse_round` with need = n - target until n <= target, a round collapses nothing
+    (stuck), or max_rounds -> {"vertices" (n,3) fp32, "faces" (m,3) int32 on the device, "rounds", "reached" (n <= target),
+    "collapses" per round}.  Buffers are sized once from the input; a round makes ONE host read (its new vertex count).  The
+    input is checked on the host first (`closed_mesh`); a mesh within the target comes back unchanged, rounds = 0.  The output is
+    a function of the input alone.  No grad, no CPU path."""
+    target, reg, max_rounds = _decimate_numbers(target, regularity, max_rounds)
+    v, f, dev = _decimate_start(verts, faces, "decimate_mesh")
+    n, m = len(v), len(f)
+    collapses = []
+    with torch.cuda.device(dev):
+        work = _Decimator(n, m, dev)
+        work.verts[0].copy_(torch.tensor(v))
+        work.faces[0].copy_(torch.from_numpy(f.astype(np.int32)))
+        at = 0
+        while n > target and len(collapses) < max_rounds:
+            new_n, m, _ = work.round(work.verts[at], work.faces[at], n, m, n - target, reg, work.verts[1 - at], work.faces[1 - at])
+            collapses.append(n - new_n)
+            n, at = new_n, 1 - at
+            if collapses[-1] == 0:
+                break
+        vertices, out_faces = work.verts[at][:n].clone(), work.faces[at][:m].clone()
+    return {"vertices": vertices, "faces": out_faces, "rounds": len(collapses), "reached": n <= target, "collapses": collapses}

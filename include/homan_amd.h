@@ -588,7 +588,7 @@ int hm_point_mesh_winding(const float* points, const float* verts, const int* fa
  * Snap.  out = closest (hm_point_mesh_distance's) iff d2 <= (snap_limit * snap_limit) * (h * h), compared in fp32, else the lattice
  * position; snap_limit is in cells, default the cell diagonal 1.7320508f (meshprep.SNAP_LIMIT).  Over a hole the half level of the
  * winding number spans the gap like a film; the limit keeps the film's vertices on the film instead of collapsing onto the rim.
- * Left out: feature-preserving placement (no QEF, no sharp edges), decimation other than through h, components thinner than a
+ * Left out: feature-preserving placement (no QEF, no sharp edges), decimation other than through h (the second stage, hm_decimate_*, is the caller's choice), components thinner than a
  * cell (they vanish).  The sign search stays brute force over every corner.
  *
  * The packed field: corner (i, j, k) is bit i & 63 of 64-bit word (k * ny + j) * W + (i >> 6), W = ceil(nx / 64);
@@ -617,6 +617,78 @@ int hm_surface_nets_emit(const void* bits, const void* cell_bits, const int* row
                          int* triangles, hipStream_t stream);
 int hm_lattice_snap(const float* lattice, const float* closest, const float* d2, long n, float snap_limit, float h, float* out,
                     int* snapped, hipStream_t stream);
+
+/* ------------------------------------------------------------------ mesh preparation, second stage: edge-collapse decimation (csrc/decimate.hip)
+ * A closed, oriented mesh (the surface nets of a FINE lattice, or a scan that is already closed) brought down to a vertex budget by
+ * memoryless quadric edge collapses in deterministic parallel rounds: ops.collapse_round / ops.decimate_mesh, meshprep.decimate and
+ * meshprep.make_watertight_detail.  With it, parts thinner than a cell of the budget lattice (a mug's wall and handle, a
+ * blade) survive the budget.  The rules below ARE the definition, pinned bit for bit by the NumPy restatement
+ * of tests/decimate_ref.py.  Floating point: doubles formed from the fp32 coordinates, one IEEE add or multiply at a time in the
+ * order written; no division, no square root, no contraction, no floating-point atomic.  The output is a function of the input
+ * alone, the same bits on every call.
+ *
+ * State: verts (n, 3) fp32, faces (m, 3) int32, closed and oriented (every undirected edge on exactly two faces, run once in each
+ * direction), no face repeats a vertex, every index in range, every vertex named by a face, coordinates finite: the CALLER's
+ * contract (the wrappers check it on the host, after dropping the vertices that no face names); 4 <= n <= 2^20, 4 <= m <= 2^22, m even.  E = 3m / 2 edges.  One round:
+ *  1 Face quadric.  a, b, c the face's corners in stored order, as doubles: N = (b - a) x (c - a), each component e1y e2z - e1z e2y
+ *    (cyclic); d = -((Nx ax + Ny ay) + Nz az); the ten numbers (NxNx, NxNy, NxNz, NyNy, NyNz, NzNz, Nx d, Ny d, Nz d, d d).  No
+ *    normalisation: the weight is the squared doubled area.
+ *  2 Vertex quadric.  Q_v = the sum over the faces at v in ascending face index, sequential adds from 0.
+ *  3 Edges.  Undirected, a < b, numbered in ascending (a, b); c = the third vertex of the face that runs a -> b, d = of the face
+ *    that runs b -> a.
+ *  4 Placement and cost.  Candidates in fp32: V[a], V[b], (V[a] + V[b]) * 0.5f.  With q = Q_a + Q_b (one add each) and p = (x, y, z)
+ *    a candidate as doubles: err = (((((((((q0 x) x + (q3 y) y) + (q5 z) z) + 2 ((q1 x) y)) + 2 ((q2 x) z)) + 2 ((q4 y) z)) + 2 (q6 x))
+ *    + 2 (q7 y)) + 2 (q8 z)) + q9.  choice = the first minimum in the order a, b, mid (a later one wins only if strictly less).
+ *    l2 = (dx dx + dy dy) + dz dz of b - a in double.  cost = err + (double)regularity * ((l2 l2) l2): the regulariser has the
+ *    quadric's units and, where every err is rounding noise (flat regions), sends the shortest edge first.
+ *  5 Validity.  All of: cost finite; m > 4; |N(a) & N(b)| == 2 (the neighbour runs are ascending, intersected by a merge);
+ *    valence(c) > 3 and valence(d) > 3 (distinct neighbours); for every face that holds exactly one of a, b, with that corner moved
+ *    to the chosen candidate: (Nox Nnx + Noy Nny) + Noz Nnz > 0 for the normals of rule 1 before and after (a face of zero area
+ *    before or after refuses the edge).
+ *  6 Rank.  The valid edges in ascending (cost, l2, edge index) get 0, 1, ...; an invalid edge has rank 2^31 - 1.
+ *  7 Selection.  m1[v] = the least rank of a valid edge at v (integer atomicMin: order-independent); m2[w] = min(m1[w], m1[v] for
+ *    v in N(w)); an edge is selected iff m2[a] == m2[b] == its rank.  No other selected edge then has an end in N[a] | N[b].
+ *  8 Budget.  need = n - target.  Of the selected edges the `need` of lowest rank stay selected.
+ *  9 Apply.  V[a] = the candidate; b becomes a in every face; the faces that now repeat a vertex (two per collapse) and the
+ *    vertices b are dropped; vertices and faces are compacted in their order.
+ * 10 Stop (the caller's loop): n <= target; a round that selects nothing (stuck; not an error); the round limit.
+ *
+ * Between the entry points the caller sorts and scans (plumbing: ascending sorts of 64-bit signed keys, stable where stated;
+ * inclusive scans of int32 flags).  Keys and orders are typed void pointers to signed 64-bit words.
+ * hm_decimate_keys: faces -> he_keys (3m words: (u n + w) n + c for the half-edge u -> w of corner u with third vertex c) and
+ *   corner_keys (3m words: u 3m + corner index).  Both are then sorted ascending (the keys are distinct).
+ * hm_decimate_offsets: he_sorted -> vertex_offsets (n + 1 ints: where vertex v's run starts in BOTH sorted arrays; the run of
+ *   he_sorted lists N(v) ascending, the run of corner_sorted its corners in ascending face index) and is_edge (3m ints: u < w).
+ *   edge_scan = the inclusive scan of is_edge: the half-edge at slot i with u < w is edge edge_scan[i] - 1.
+ * hm_decimate_costs: rules 1-5 -> quadrics (n, 10) doubles, edges (E, 4) ints a b c d, choice (E) 0 / 1 / 2, cost (E), l2 (E)
+ *   doubles, valid (E) 0 / 1, cost_keys and l2_keys (E words each: the doubles' bits in an order-preserving signed form; 2^63 - 1
+ *   for an invalid edge).  order (E words) = the edge indices sorted stably by l2_keys, then stably by cost_keys.
+ * hm_decimate_select: rules 6-7 -> rank (E), m1, m2 (n), selected (E) 0 / 1, selected_by_rank (E: the flag of the edge of rank r
+ *   at r, else 0), and the cleared remap (n: v), vertex_keep (n: 1), moved (n: -1).  selected_scan = the inclusive scan of
+ *   selected_by_rank.
+ * hm_decimate_mark: rules 8-9, first half: selected is cleared where selected_scan[rank] > need; for those that stay remap[b] = a,
+ *   vertex_keep[b] = 0, moved[a] = the edge; face_keep (m) = 0 for a face two of whose mapped corners agree.  vertex_scan,
+ *   face_scan = the inclusive scans of the keeps; vertex_scan[n - 1] is the new n (the round's ONE host read).
+ * hm_decimate_compact: out_verts (max_vertices, 3) and out_faces (max_faces, 3): kept vertex v at vertex_scan[v] - 1, with the
+ *   candidate's position if moved[v] names an edge; kept face f at face_scan[f] - 1, corners vertex_scan[remap[.]] - 1.  An element
+ *   at or beyond a capacity is not written; a capacity of 0 skips that output (its pointer may be NULL).
+ * Every launch goes on `stream`; nothing is allocated, synchronised or read back.  HM_ERR_BAD_ARG, nothing enqueued, outputs
+ * untouched: a NULL pointer (other than the optional ones), n or m outside the admitted range or m odd, a regularity that is not
+ * finite and >= 0, a negative need or capacity, a misaligned key or order array.
+ * ALIGNMENT: he_keys, corner_keys, he_sorted, corner_sorted, cost_keys, l2_keys, order 8 bytes (typed void pointers: 64-bit words). */
+int hm_decimate_keys(const int* faces, int n, int m, void* he_keys, void* corner_keys, hipStream_t stream);
+int hm_decimate_offsets(const void* he_sorted, int n, int m, int* vertex_offsets, int* is_edge, hipStream_t stream);
+int hm_decimate_costs(const float* verts, const int* faces, const void* he_sorted, const void* corner_sorted,
+                      const int* vertex_offsets, const int* edge_scan, int n, int m, float regularity, double* quadrics, int* edges,
+                      int* choice, double* cost, double* l2, int* valid, void* cost_keys, void* l2_keys, hipStream_t stream);
+int hm_decimate_select(const int* edges, const int* valid, const void* order, const void* he_sorted, const int* vertex_offsets, int n,
+                       int m, int* rank, int* m1, int* m2, int* selected, int* selected_by_rank, int* remap, int* vertex_keep,
+                       int* moved, hipStream_t stream);
+int hm_decimate_mark(const int* faces, const int* edges, const int* rank, const int* selected_scan, int need, int n, int m,
+                     int* selected, int* remap, int* vertex_keep, int* moved, int* face_keep, hipStream_t stream);
+int hm_decimate_compact(const float* verts, const int* faces, const int* edges, const int* choice, const int* remap, const int* moved,
+                        const int* vertex_keep, const int* vertex_scan, const int* face_keep, const int* face_scan, int n, int m,
+                        int max_vertices, int max_faces, float* out_verts, int* out_faces, hipStream_t stream);
 
 /* ------------------------------------------------------------------ surface contact loss (csrc/surfcontact.hip)
  * Attraction of the points outside a mesh and repulsion of the points inside it, each a tanh-saturated exact distance to the

@@ -4,7 +4,7 @@ watertight `X_proc.obj` of at most `--vertex_nb` vertices and the pickle `X_proc
 (homan_amd/meshprep.py simplify_mesh; the walk of the reference's shapemeshprocess.py, without its two external programs).
 A source whose pickle already exists is skipped.
 
-usage: python tools/prepare_meshes.py [--file_path extra_data/objmodels.txt] [--vertex_nb 1000]"""
+usage: python tools/prepare_meshes.py [--file_path extra_data/objmodels.txt] [--vertex_nb 1000] [--detail_resolution 64]"""
 import argparse
 import os
 import sys
@@ -23,6 +23,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--file_path", default="extra_data/objmodels.txt", help="text file with one mesh path per line")
     ap.add_argument("--vertex_nb", type=int, default=1000, help="vertex budget of the prepared mesh")
+    ap.add_argument("--detail_resolution", type=int, default=None,
+                    help="off by default; an integer in [2, 256]: surface nets at that fine lattice, then edge-collapse "
+                         "decimation to --vertex_nb (keeps parts thinner than a cell of the budget lattice)")
     ap.add_argument("--manifold_path", default=None, help="accepted for the reference's command line; unused")
     ap.add_argument("--acvd_path", default=None, help="accepted for the reference's command line; unused")
     a = ap.parse_args(argv)
@@ -36,7 +39,11 @@ def main(argv=None):
             continue
         if not os.path.exists(src):
             raise FileNotFoundError(src)
-        mesh = meshprep.simplify_mesh(src, target, vert_nb=a.vertex_nb)
+        extra = {} if a.detail_resolution is None else {"detail_resolution": a.detail_resolution}
+        mesh = meshprep.simplify_mesh(src, target, vert_nb=a.vertex_nb, **extra)
+        if "rounds" in mesh:
+            print(f"{src}: {mesh['detail_vertices']} vertices off the fine lattice, {mesh['rounds']} rounds of collapses, "
+                  f"budget {'met' if mesh['reached'] else 'NOT met'}")
         print(f"{src}: {len(mesh['vertices'])} vertices, {len(mesh['faces'])} faces at resolution {mesh['resolution']} -> {target}")
         done += 1
     return done
