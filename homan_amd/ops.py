@@ -764,6 +764,50 @@ def priors(pca, s_obj, m_obj, s_hand, m_hand):
     return _Priors.apply(pca, s_obj, m_obj, s_hand, m_hand)
 
 
+class _KeypointTerms(torch.autograd.Function):
+    """hm_keypoint_terms_clips (csrc/handinit.hip; no reference counterpart): the 21 regressed keypoints of camera-space MANO
+    vertices against 2-D / 3-D targets.  Differentiable output: total (C,) = lw_kp2d L2d + lw_kp3d L3d per clip."""
+
+    @staticmethod
+    def forward(ctx, verts, W, camintr, kp2d, c2, s, kp3d, c3, sigma, znear, clip_len, lw_kp2d, lw_kp3d):
+        verts = _f32(verts)
+        N = verts.shape[0]
+        C = N // clip_len if clip_len > 0 else 0
+        dev = verts.device
+        keypoints, unit = torch.empty(N, 21, 3, device=dev), torch.empty_like(verts)
+        row_parts, tickets = torch.empty(N, 2, device=dev), torch.zeros(max(C, 1), dtype=torch.int32, device=dev)
+        out = torch.empty(max(C, 1), 2, device=dev)
+        _lib.check(_lib.lib().hm_keypoint_terms_clips(_p(verts), _p(W), _p(camintr), _p(kp2d), _p(c2), _p(s), _p(kp3d), _p(c3),
+                                                      float(sigma), float(znear), float(lw_kp2d), float(lw_kp3d), N, int(clip_len),
+                                                      _p(keypoints), _p(unit), _p(row_parts), _p(tickets), _p(out), 2,
+                                                      _lib.stream()), "hm_keypoint_terms_clips")
+        ctx.save_for_backward(unit)
+        ctx.clip_len = int(clip_len)
+        l2, l3 = out[:, 0], out[:, 1]
+        total = float(lw_kp2d) * l2 + float(lw_kp3d) * l3
+        ctx.mark_non_differentiable(l2, l3, keypoints)
+        return total, l2, l3, keypoints
+
+    @staticmethod
+    def backward(ctx, g_total, _g2, _g3, _gk):
+        (unit,) = ctx.saved_tensors
+        B = ctx.clip_len
+        g_total = _f32(g_total)
+        g = torch.cat([_scale_by(unit[c * B:(c + 1) * B], g_total[c]) for c in range(unit.shape[0] // B)])
+        return (g,) + (None,) * 12
+
+
+def keypoint_terms(verts_world, W, camintr, kp2d, c2, s, kp3d=None, c3=None, sigma=1.0, znear=0.01, clip_len=1, lw_kp2d=1.0,
+                   lw_kp3d=1.0):
+    """verts_world (N,778,3) camera-space MANO vertices, W (21,778) (handinit.keypoint_regressor), camintr (N,3,3) pixels, kp2d
+    (N,21,2) pixels, c2 (N,21) >= 0, s (N) box scales in pixels, kp3d (N,21,3) / c3 (N,21) optional, clips of clip_len rows
+    -> (total (C,), L2d (C,), L3d (C,), keypoints (N,21,3)); the gradient flows through `total` = lw_kp2d L2d + lw_kp3d L3d
+    (the rules: include/homan_amd.h)."""
+    f = lambda t: None if t is None else _f32(t)
+    return _KeypointTerms.apply(verts_world, f(W), f(camintr), f(kp2d), f(c2), f(s), f(kp3d), f(c3), sigma, znear, clip_len,
+                                lw_kp2d, lw_kp3d)
+
+
 class _InterLoss(torch.autograd.Function):
     """reference homan/losses.py:199-242 ('centroid'), gating :98-139; returns the un-normalised sum, shape (1,)."""
 

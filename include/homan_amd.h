@@ -974,6 +974,55 @@ int hm_collision_fwd_clips(const float* verts0, const int* faces0, int V0, int F
 int hm_log_total_clips(float* vals, const float* weights, int n, const int* step, int max_steps, float* log, int nclips,
                        hipStream_t stream);
 
+/* ------------------------------------------------------------------ hand initialisation from keypoints (csrc/handinit.hip)
+ * Fits MANO to 21 2-D (and optionally 3-D) keypoints per frame: homan_amd/handinit.py.  Not in the reference tree, whose hand
+ * start comes from a pose network (homan/mocap.py:34-113): the rules below ARE the definition, pinned bit
+ * for bit by the fp32 NumPy restatement of tests/handinit_ref.py.  Every operation is fp32 IEEE without contraction, written
+ * below with its parentheses; a sum "from 0" starts at 0.0f and adds its addends one at a time in the stated order.
+ *
+ * A row is one frame of one candidate; clip c = rows [c * clip_len, (c + 1) * clip_len) is one candidate track, N = C * clip_len.
+ * verts_world (N,778,3): the camera-space vertices hm_mano_fwd_clips writes.  W (21,778): the keypoint regressor of the hand's
+ * side.  camintr (N,3,3) in pixels (fx, cx, fy, cy = entries 0, 2, 4, 5).  kp2d (N,21,2) pixels, c2 (N,21) >= 0, s (N) > 0 the
+ * frame's box scale in pixels.  kp3d (N,21,3) metres relative to keypoint 0 and c3 (N,21): both or neither.
+ *
+ * Two sums are used throughout.  TREE64(a_0 .. a_63): a_l += a_(l ^ o) for o = 32, 16, 8, 4, 2, 1.  BLOCKSUM(x_0 .. x_(n-1)): thread
+ * t of 256 adds x_t, x_(t+256), ... from 0; TREE64 over each of the four groups of 64 consecutive threads gives w0 .. w3; the
+ * result is ((w0 + w1) + w2) + w3.
+ *   X[n,k,c]  = TREE64 over l of (the sum from 0 over v = l, l + 64, ... < 778 of W[k,v] * verts_world[n,v,c])   -> keypoints (N,21,3)
+ *   S2[clip]  = BLOCKSUM of the clip's clip_len * 21 values c2 in memory order, S3 the same of c3 (0 without kp3d)
+ *   2-D term of (n,k), with (x, y, z) = X[n,k], only if c2 > 0 (otherwise cost 0, gradient 0, kp2d[n,k] is not read: it may be NaN):
+ *     z > znear:  px = (fx * x) / z + cx, py = (fy * y) / z + cy, rx = (px - kp2d.x) / s[n], ry likewise, u = rx * rx + ry * ry,
+ *                 den = sigma * sigma + u, cost = c2 * ((sigma * sigma * u) / den)          (Geman-McClure)
+ *                 g = (c2 * (q * q)) * (lw_kp2d / S2) with q = sigma * sigma / den; gpx = g * ((2 * rx) / s[n]), gpy likewise;
+ *                 dX = (gpx * (fx / z), gpy * (fy / z), -((gpx * (fx * x) + gpy * (fy * y)) / (z * z)))
+ *     z <= znear: cost = c2 * (sigma * sigma), gradient 0 (a candidate cannot win by hiding keypoints behind the camera)
+ *   3-D term of (n,k), only if c3 > 0: d = (X[n,k] - X[n,0]) - kp3d[n,k], cost = c3 * ((d.x * d.x + d.y * d.y) + d.z * d.z),
+ *     h = ((2 * c3) * (lw_kp3d / S3)) * d; G[n,k] = dX + h, and G[n,0] then loses the sum from 0 over k = 0 .. 20 of h[n,k].
+ *   lw / S is 0 where S == 0.
+ *   unit_grad[n,v,c] = the sum from 0 over k = 0 .. 20 of W[k,v] * G[n,k,c] = d (lw_kp2d L2d + lw_kp3d L3d) / d verts_world: ONE
+ *     entry of the g_terms of hm_mano_bwd_rigid_clips, weight 1.
+ *   row_parts (N,2) = {TREE64 of the row's 21 costs (lanes 21 .. 63 hold 0), 2-D; the same, 3-D}
+ *   out2[c * out_stride + 0] = L2d = BLOCKSUM(the clip's row_parts[.,0], rows ascending) / S2, 0 where S2 == 0; [+ 1] = L3d alike.
+ * One launch, one workgroup per row; the clip's last workgroup (a ticket) forms L2d / L3d.  No floating-point atomics: the bits
+ * do not depend on the run, nor on where a clip stands in the batch or how many clips there are.
+ * row_parts: caller-owned (N,2) output.  clip_tickets: C ints, zero-filled ONCE by the caller (they reset themselves).
+ * HM_ERR_BAD_ARG, nothing launched, outputs untouched: a NULL pointer other than the pair kp3d / c3 (or only one of that pair),
+ * N <= 0, clip_len <= 0, N not a multiple of clip_len, sigma <= 0 (or NaN). */
+int hm_keypoint_terms_clips(const float* verts_world, const float* W, const float* camintr, const float* kp2d, const float* c2,
+                            const float* s, const float* kp3d, const float* c3, float sigma, float znear, float lw_kp2d,
+                            float lw_kp3d, int N, int clip_len, float* keypoints, float* unit_grad, float* row_parts,
+                            int* clip_tickets, float* out2, int out_stride, hipStream_t stream);
+/* The tail of a step of the keypoint fit, one workgroup per clip.  vals (C, vals_stride >= 8): row c holds {L2d, L3d, Lpca, -, -,
+ * Lsmooth, Lbeta, total}: slots 0 / 1 from hm_keypoint_terms_clips, 2 .. 4 from hm_priors_fwd_clips, 5 from hm_smooth_fwd_clips
+ * (all called with out_stride = vals_stride).  betas (N,10): Lbeta = BLOCKSUM(the clip's betas squared, memory order) * inv with
+ * inv = 1 / (10 clip_len); g_betas (N,10; optional) += lw_beta * ((2 * beta) * inv), after the MANO backward has written it;
+ * total = (((lw_kp2d * L2d + lw_kp3d * L3d) + lw_pca * Lpca) + lw_beta * Lbeta) + lw_smooth * Lsmooth.  log (max_steps, C, 8)
+ * optional: row min(step[0], max_steps - 1) receives the clips' eight values (step: the device counter of hm_adam_step, read
+ * BEFORE that step's launch).  HM_ERR_BAD_ARG as above, and for vals_stride < 8 or a log without step / max_steps > 0. */
+int hm_handinit_finish_clips(const float* betas, float* g_betas, int N, int clip_len, float* vals, int vals_stride,
+                             float lw_kp2d, float lw_kp3d, float lw_pca, float lw_beta, float lw_smooth, const int* step,
+                             int max_steps, float* log, hipStream_t stream);
+
 /* ------------------------------------------------------------------ measurement / debug hooks (synchronous)
  * hm_bench_sil_kernels: one full silhouette forward + backward to populate the workspace, then `reps` launches of the
  * raster kernel, of the edge-sweep kernel and of the line-source kernel, each series bracketed by two HIP events on
