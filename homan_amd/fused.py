@@ -213,6 +213,10 @@ class FusedStepper:
             # (checked before anything is built: mode="auto" and ClipFitter fall back as they do for sil_mode="soft")
             raise NotImplementedError("lw_surf_attr / lw_surf_rep: the surface contact loss is not in the fused launch sequence "
                                       "(mode='graph' or 'eager')")
+        if float(loss_weights.get("lw_depth_obs", 0)) > 0:
+            # (one clip or a batch of clips alike: the term lives in HOMan.forward only)
+            raise NotImplementedError("lw_depth_obs: the observed-depth term is not in the fused launch sequence "
+                                      "(mode='graph' or 'eager')")
         for one in (model.models if isinstance(model, ClipBatch) else model if isinstance(model, (list, tuple)) else [model]):
             if len(one.hand_sides) not in (1, 2):
                 raise NotImplementedError("one or two hands per frame")

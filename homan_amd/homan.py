@@ -53,13 +53,17 @@ def weakcam_persp_trans(cams, K, image_size=640, reference_depth=1.0):
 def clip_tensors(translations_object, rotations_object, verts_object_og, translations_hand, rotations_hand, verts_hand_og,
                  ref_verts2d_hand, mano_trans, mano_rot, mano_betas, mano_pca_pose, masks_object, masks_hand,
                  camintr_rois_object, camintr_rois_hand, target_masks_object, target_masks_hand, cams_hand=None, camintr=None,
-                 int_scale_init=1.0, hand_proj_mode="persp", device=None, **_not_clip_data):
+                 int_scale_init=1.0, hand_proj_mode="persp", device=None, depth_maps=None, **_not_clip_data):
     """The data arguments of the constructor (reference homan/homan.py:27-60) -> ordered {name: tensor} of everything in a
     model that depends on the clip, in the form the model stores it (:62-166; in the constructor's registration order).  The ONE
     place where raw clip inputs are converted: HOMan.__init__ registers these, HOMan.load_clip copies them in place.  Raises
     the ortho refusals on the host input (forward may run inside a stream capture).  Without `device` nothing touches a
     device; with it, what is DERIVED (mask comparisons, constants) is formed there - the clip's own arrays stay where the
-    caller has them, so that the consumer's copy is their one transfer."""
+    caller has them, so that the consumer's copy is their one transfer.
+    depth_maps (optional, a homan_amd extra: the observed-depth term): (B, S, S) sensor depth in METRES, in
+    the camera of `camintr` and registered pixel for pixel with the instance masks, i.e. at THEIR resolution - bringing raw sensor
+    frames (another resolution, millimetres, uint16) to that grid is the caller's job.  NaN, infinite, zero, negative and
+    out-of-range values mark pixels without a measurement.  Adds the buffer `depth_maps`."""
     f32 = lambda t: torch.as_tensor(t).detach().float()
     rot6d = lambda r: (matrix_to_rot6d(r) if r.shape[-1] == 3 else r).contiguous()
     const = lambda shape, value: torch.full(tuple(shape), float(value), device=device)
@@ -93,6 +97,13 @@ def clip_tensors(translations_object, rotations_object, verts_object_og, transla
     if masks_hand is not None:
         out["masks_human"] = torch.as_tensor(masks_hand).detach()
     out["masks_object"] = masks_object.unsqueeze(0) if masks_object.dim() == 2 else masks_object
+    if depth_maps is not None:
+        depth_maps = f32(depth_maps)
+        want = (translations_object.shape[0],) + tuple(out["masks_object"].shape[-2:])
+        if tuple(depth_maps.shape) != want:
+            raise ValueError(f"depth_maps of shape {tuple(depth_maps.shape)}: expected {want} (one map per frame, at the "
+                             "instance masks' resolution)")
+        out["depth_maps"] = depth_maps.contiguous()
     return out
 
 
@@ -106,8 +117,21 @@ class HOMan(nn.Module):
                  # homan_amd extensions (keyword-only use)
                  mano_model=None, mano_root="extra_data/mano", rend_size=constants.REND_SIZE, sync_metrics=True,
                  ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4, surface_contact_thresh=constants.CONTACT_THRESH,
-                 surface_collision_thresh=constants.COLLISION_THRESH, surface_two_way=False, surface_contact_zones="all"):
+                 surface_collision_thresh=constants.COLLISION_THRESH, surface_two_way=False, surface_contact_zones="all",
+                 depth_maps=None, depth_obs_delta=0.03, depth_obs_layers="all"):
         # (host-side checks of the options first: no device is touched before they pass)
+        if depth_obs_layers not in ("all", "object", "hand"):
+            raise ValueError(f"depth_obs_layers {depth_obs_layers} not in [all|object|hand]")
+        if not 0 < float(depth_obs_delta) <= 1:
+            raise ValueError(f"depth_obs_delta {depth_obs_delta} must lie in (0, 1] (metres; the kernel's exact sums are sized for it)")
+        if depth_maps is not None:
+            want = (translations_object.shape[0], int(image_size), int(image_size))
+            if tuple(torch.as_tensor(depth_maps).shape) != want:
+                raise ValueError(f"depth_maps of shape {tuple(torch.as_tensor(depth_maps).shape)}: expected (B, image_size, "
+                                 f"image_size) = {want}")
+            if int(image_size) > 1024:
+                # hm_depth_obs_fwd keeps a frame's pixel counts in 21-bit fields, like the ordinal depth term's kernel
+                raise NotImplementedError(f"depth_maps: image_size {image_size} > 1024 (scale maps, masks and intrinsics down)")
         if surface_contact_zones not in ("all", "tips"):
             raise ValueError(f"surface_contact_zones {surface_contact_zones} not in [all|tips]")
         for name, c in (("surface_contact_thresh", surface_contact_thresh), ("surface_collision_thresh", surface_collision_thresh)):
@@ -139,7 +163,8 @@ class HOMan(nn.Module):
         for name, t in clip_tensors(translations_object, rotations_object, verts_object_og, translations_hand, rotations_hand,
                                     verts_hand_og, ref_verts2d_hand, mano_trans, mano_rot, mano_betas, mano_pca_pose,
                                     masks_object, masks_hand, camintr_rois_object, camintr_rois_hand, target_masks_object,
-                                    target_masks_hand, cams_hand, camintr, int_scale_init, hand_proj_mode).items():
+                                    target_masks_hand, cams_hand, camintr, int_scale_init, hand_proj_mode,
+                                    depth_maps=depth_maps).items():
             if name == "camintr":       # (the topology's place in the reference's registration order, homan.py:144-151)
                 self.register_buffer("faces_object", faces_object.detach().clone())
                 # white per-face textures of the single-mesh depth renders (state_dict keys)
@@ -201,6 +226,10 @@ class HOMan(nn.Module):
             raise NotImplementedError(f"ordinal depth term: image_size {image_size} > 1024 (rendered at image_size; scale the "
                                       "instance masks and intrinsics down, or leave ordinal_depth off)")
         self._depth_state = None
+        # observed-depth term (a homan_amd extra): on when forward() is given lw_depth_obs > 0; needs the
+        # buffer `depth_maps`.  delta = 0.03 m is an UNTUNED default.
+        self.depth_obs_delta, self.depth_obs_layers = float(depth_obs_delta), depth_obs_layers
+        self._depth_obs_scratch = None
         with torch.no_grad():
             self.verts_hand_init = self.get_verts_hand()[0].detach().clone()
             self.verts_object_init = self.get_verts_object()[0].detach().clone()
@@ -218,6 +247,10 @@ class HOMan(nn.Module):
         if faces_object is not None and not torch.equal(torch.as_tensor(faces_object)[0].cpu(), self.faces_object[0].cpu()):
             raise ValueError("load_clip: other object topology")
         new = clip_tensors(**dict(clip, hand_proj_mode=self.hand_proj_mode, device=self.translations_object.device))
+        if hasattr(self, "depth_maps") and "depth_maps" not in new:
+            raise ValueError("load_clip: the model was built with depth_maps; every later clip must bring depth_maps too")
+        if "depth_maps" in new and not hasattr(self, "depth_maps"):
+            raise ValueError("load_clip: the clip brings depth_maps, the model was built without (build it with depth_maps)")
         pairs = [(name, getattr(self, name), src) for name, src in new.items() if hasattr(self, name)]
         for name, dst, src in pairs:
             if tuple(src.shape) != tuple(dst.shape):
@@ -418,26 +451,48 @@ class HOMan(nn.Module):
         ctxs, masks = self.depth_layers()
         return ctxs[0], ctxs[1], masks[0], masks[1]
 
-    def compute_ordinal_depth_loss(self, verts_object=None, verts_hand=None):
+    def render_depth_layers(self, verts_object, verts_hand, layers=None):
+        """{layer: (silhouette, depth)} of the layers [object, hand 0, (hand 1)] named in `layers` (default: all), each rendered
+        ONCE at the full-image intrinsics on its own context of depth_layers() (reference homan.py:391,403-417: one render per
+        hand over its strided rows).  Every depth term of a forward consumes these renders; autograd sums their gradient images
+        into one depth backward per layer."""
+        ctxs, _ = self.depth_layers()
+        verts = [verts_object] + ([verts_hand] if self.hand_nb == 1 else
+                                  [verts_hand[h::self.hand_nb].contiguous() for h in range(self.hand_nb)])
+        return {l: ops.depth_render(verts[l], self.camintr, ctxs[l], 1.0)
+                for l in (range(len(ctxs)) if layers is None else layers)}
+
+    def compute_ordinal_depth_loss(self, verts_object=None, verts_hand=None, renders=None):
         """reference homan/homan.py:384-419: render object and hand depth at the full-image intrinsics, compare their
-        ordering with the instance masks (lossutils.py:133-169); with two hands the three layers pair-wise."""
-        if verts_object is None:
-            verts_object, _ = self.get_verts_object()
-        if verts_hand is None:
-            verts_hand, _ = self.get_verts_hand()
-        if self.hand_nb != 1:
-            # layers [object, hand 0, hand 1] (homan.py:403-417: one render per hand over its strided rows), every pair of them
-            ctxs, masks = self.depth_layers()
-            sils, deps = [], []
-            for verts, ctx in zip([verts_object] + [verts_hand[h::self.hand_nb].contiguous() for h in range(self.hand_nb)], ctxs):
-                sil, dep = ops.depth_render(verts, self.camintr, ctx, 1.0)
-                sils.append(sil)
-                deps.append(dep)
-            return {"loss_depth": ops.ordinal_depth_loss_layers(deps, sils, masks, self.reduce_ws)}
-        ctx_o, ctx_h, m_o, m_h = self.depth_contexts()
-        sil_o, dep_o = ops.depth_render(verts_object, self.camintr, ctx_o, 1.0)
-        sil_h, dep_h = ops.depth_render(verts_hand, self.camintr, ctx_h, 1.0)
-        return {"loss_depth": ops.ordinal_depth_loss(dep_o, dep_h, sil_o, sil_h, m_o, m_h, self.reduce_ws)}
+        ordering with the instance masks (lossutils.py:133-169); with two hands the three layers pair-wise.
+        renders: render_depth_layers() of this forward, when another depth term shares them."""
+        if renders is None:
+            if verts_object is None:
+                verts_object, _ = self.get_verts_object()
+            if verts_hand is None:
+                verts_hand, _ = self.get_verts_hand()
+            renders = self.render_depth_layers(verts_object, verts_hand)
+        _, masks = self.depth_layers()
+        sils, deps = [renders[l][0] for l in range(len(masks))], [renders[l][1] for l in range(len(masks))]
+        # (two layers: the object-hand pair of the two-layer kernels; three: every pair of them)
+        return {"loss_depth": ops.ordinal_depth_loss_layers(deps, sils, masks, self.reduce_ws)}
+
+    def depth_obs_layer_ids(self):
+        """the layers of depth_layers() the observed-depth term compares, by the option depth_obs_layers"""
+        return {"all": list(range(1 + self.hand_nb)), "object": [0], "hand": list(range(1, 1 + self.hand_nb))}[self.depth_obs_layers]
+
+    def compute_depth_obs_loss(self, renders, sole_consumer):
+        """({"loss_depth_obs"}, {"depth_obs_mae", "depth_obs_valid_share"}): the observed-depth term (ops.depth_obs_loss; the rule is
+        in include/homan_amd.h and DESIGN.md section 7) on the layers of depth_obs_layers, against the buffer `depth_maps`.
+        sole_consumer: no other term reads these renders' depth images, so their backward may take the sparse path."""
+        ids = self.depth_obs_layer_ids()
+        ctxs, masks = self.depth_layers()
+        if self._depth_obs_scratch is None:
+            self._depth_obs_scratch = ops.DepthObsScratch(len(ids), self.depth_maps.shape[0], self.depth_maps.device)
+        loss, mae, share = ops.depth_obs_loss([renders[l][1] for l in ids], [renders[l][0] for l in ids], [masks[l] for l in ids],
+                                              self.depth_maps, self.depth_obs_delta, self._depth_obs_scratch,
+                                              [ctxs[l] for l in ids] if sole_consumer else None)
+        return {"loss_depth_obs": loss}, {"depth_obs_mae": mae, "depth_obs_valid_share": share}
 
     def compute_surface_contact_loss(self, verts_hand, verts_object):
         """({"loss_surf_attr", "loss_surf_rep"}, {"surf_inside_share"}) on the model's options (lossutils)"""
@@ -452,9 +507,13 @@ class HOMan(nn.Module):
         """reference homan.py:421-508: a loss whose weight is zero is not computed.  The one exception to "None computes
         everything" is the surface contact loss, an extra: it runs only when loss_weights holds a positive lw_surf_attr or
         lw_surf_rep (the term with a positive weight is returned), so forward(None) and weight sets without those keys
-        return the reference's keys."""
+        return the reference's keys.  The observed-depth term, the other extra, follows the same rule on lw_depth_obs (and needs
+        the model's depth_maps)."""
         lw = loss_weights
         on = lambda key: lw is None or lw[key] > 0
+        want_obs = lw is not None and lw.get("lw_depth_obs", 0) > 0
+        if want_obs and not hasattr(self, "depth_maps"):
+            raise ValueError("lw_depth_obs > 0: the model has no sensor depth; build it with depth_maps=(B, image_size, image_size)")
         loss_dict, metric_dict = {}, {}
         if self.optimize_mano:      # MANO is evaluated once and shared by the reference's two get_verts_hand calls
             self._mano_cache = None
@@ -506,10 +565,19 @@ class HOMan(nn.Module):
             loss_dict["loss_scale_obj"] = l_so
         if want_sh:
             loss_dict["loss_scale_hand"] = l_sh
-        if (lw is None or lw["lw_depth"] > 0) and self.ordinal_depth:
-            loss_dict.update(self.compute_ordinal_depth_loss(verts_object, verts_hand))
-        elif lw is None or lw["lw_depth"] > 0:
+        want_ord = lw is None or lw["lw_depth"] > 0
+        if want_ord and not self.ordinal_depth:
             # reference homan.py:506-507 calls lossutils.compute_ordinal_depth_loss() without its arguments
             raise TypeError("compute_ordinal_depth_loss() missing 3 required positional arguments: "
                             "'masks', 'silhouettes', and 'depths'")
+        # both depth terms consume ONE render per layer (a context holds one render's intermediates)
+        renders = None
+        if want_ord or want_obs:
+            renders = self.render_depth_layers(verts_object, verts_hand, None if want_ord else self.depth_obs_layer_ids())
+        if want_ord:
+            loss_dict.update(self.compute_ordinal_depth_loss(renders=renders))
+        if want_obs:
+            l, m = self.compute_depth_obs_loss(renders, sole_consumer=not want_ord)
+            loss_dict.update(l)
+            metric_dict.update({k: v.item() if self.sync_metrics else v.detach() for k, v in m.items()})
         return loss_dict, metric_dict

@@ -124,7 +124,8 @@ def optimize_hand_object(person_parameters, object_parameters, class_name="defau
                          # homan_amd extensions
                          mode="auto", mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr",
                          sil_sigma=1e-4, surface_contact_thresh=0.010, surface_collision_thresh=0.020,
-                         surface_two_way=False, surface_contact_zones="all"):
+                         surface_two_way=False, surface_contact_zones="all", depth_maps=None, depth_obs_delta=0.03,
+                         depth_obs_layers="all"):
     auto = mode == "auto"
     if auto:
         # the fused launch sequence whenever FusedStepper accepts the configuration (every BASELINE config), else the same
@@ -136,7 +137,8 @@ def optimize_hand_object(person_parameters, object_parameters, class_name="defau
                         image_size, mano_model, rend_size, sync_metrics=(mode == "eager"), ordinal_depth=ordinal_depth,
                         sil_mode=sil_mode, sil_sigma=sil_sigma,
                         surface_contact_thresh=surface_contact_thresh, surface_collision_thresh=surface_collision_thresh,
-                        surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones)
+                        surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones, depth_maps=depth_maps,
+                        depth_obs_delta=depth_obs_delta, depth_obs_layers=depth_obs_layers)
     # visualisation frames every `viz_step` iterations (reference jointopt.py:158-176), only when the caller hands the
     # input images over; the videos the reference assembles from them (libyana np2vid, :193-200) are not built
     imgs = OrderedDict()

@@ -130,7 +130,10 @@ def build_model(person_parameters, object_parameters, class_name="default", objv
                 camintr=None, hand_proj_mode="persp", optimize_mano=False, optimize_mano_beta=True,
                 optimize_object_scale=False, state_dict=None, image_size=640, mano_model=None, rend_size=256,
                 sync_metrics=True, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4,
-                surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all"):
+                surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all",
+                depth_maps=None, depth_obs_delta=0.03, depth_obs_layers="all"):
+    """depth_maps (the observed-depth term, lw_depth_obs) is an ARGUMENT, next to camintr: the per-frame dicts that
+    collate_inputs reads keep the reference's fields.  (B, image_size, image_size) metres, see homan.clip_tensors."""
     kw = collate_inputs(person_parameters, object_parameters, objvertices, objfaces)
     model = HOMan(camintr=camintr, class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode,
                   optimize_mano=optimize_mano, optimize_mano_beta=optimize_mano_beta,
@@ -138,7 +141,8 @@ def build_model(person_parameters, object_parameters, class_name="default", objv
                   rend_size=rend_size, sync_metrics=sync_metrics, ordinal_depth=ordinal_depth, sil_mode=sil_mode,
                   sil_sigma=sil_sigma,
                   surface_contact_thresh=surface_contact_thresh, surface_collision_thresh=surface_collision_thresh,
-                  surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones, **kw)
+                  surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones, depth_maps=depth_maps,
+                  depth_obs_delta=depth_obs_delta, depth_obs_layers=depth_obs_layers, **kw)
     if state_dict is not None:
         model.load_state_dict(state_dict, strict=False)
     return model

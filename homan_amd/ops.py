@@ -194,6 +194,25 @@ class SilhouetteContext:
         _lib.check(_lib.lib().hm_sil_invalidate_outputs(_lib.ptr(self.workspace), self.B, self.V, self.F, self.S,
                                                         _lib.stream()), "hm_sil_invalidate_outputs")
 
+    # ---- the non-zero flags of a depth-gradient image (hm_depth_bwd_sparse), handed from the loss term that wrote image and flags
+    # in one launch to the depth backward of this context's render: no second copy of the image, the flags ride beside it
+    _gflags = None
+    last_depth_bwd = None        # "sparse" / "dense": the path the last depth backward on this context took
+
+    def offer_gflags(self, grad_image, flags):
+        """`flags` describe `grad_image` as it is NOW; they are taken (once) only by a depth backward that receives that very
+        tensor, unmodified - a gradient autograd has summed with another term's is a different or a re-versioned tensor"""
+        self._gflags = (grad_image, grad_image._version, flags)
+
+    def take_gflags(self, grad_image):
+        held, self._gflags = self._gflags, None
+        if held is None or self.padded or self.S % 64 != 0:
+            return None
+        img, version, flags = held
+        same = (img.data_ptr() == grad_image.data_ptr() and img.shape == grad_image.shape and grad_image.is_contiguous() and
+                grad_image.dtype == torch.float32 and grad_image._version == version)
+        return flags if same else None
+
     def parts(self):
         """(B,F,3,2) float64: per-(face, corner) NDC gradients of the last backward (exact sums, see include/homan_amd.h)"""
         out = torch.empty(self.B, self.F, 3, 2, dtype=torch.float64, device=self.workspace.device)
@@ -456,6 +475,16 @@ class _DepthRender(torch.autograd.Function):
         verts, K = ctx.saved_tensors
         sctx = ctx.sctx
         grad_verts = torch.empty_like(verts)
+        # a gradient image that arrives exactly as a loss term's backward left it, with that term's non-zero flags
+        # (offer_gflags), takes the sparse backward: same result, faces and frames off the flagged segments are not walked
+        gflags = sctx.take_gflags(g_depth)
+        sctx.last_depth_bwd = "dense" if gflags is None else "sparse"
+        if gflags is not None:
+            _lib.check(_lib.lib().hm_depth_bwd_sparse(
+                _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size), _lib.ptr(g_depth),
+                _lib.ptr(sctx.adj_off), _lib.ptr(sctx.adj_items), _lib.ptr(grad_verts), _lib.ptr(gflags),
+                _lib.ptr(sctx.workspace), _lib.stream()), "hm_depth_bwd_sparse")
+            return grad_verts, None, None, None
         _lib.check(_lib.lib().hm_depth_bwd(
             _lib.ptr(verts), _lib.ptr(K), sctx.B, sctx.V, sctx.F, sctx.S, float(ctx.orig_size),
             _lib.ptr(sctx.pad(_f32(g_depth))),
@@ -548,6 +577,87 @@ def ordinal_depth_loss_layers(depths, sils, masks, rws):
     for val, pairs in terms:
         loss = loss + torch.where(pairs > 0, val * (pairs / total), torch.zeros_like(val))
     return loss
+
+
+class DepthObsScratch:
+    """The caller's scratch of hm_depth_obs_fwd for L layers of B frames: the records' integer words and the ticket, zero-filled
+    once (every call leaves them zero).  Allocated outside any stream capture and kept by whoever calls the term repeatedly."""
+
+    def __init__(self, layers, batch, device):
+        nbytes = _lib.lib().hm_depth_obs_acc_bytes(int(layers), int(batch))
+        if nbytes == 0:
+            raise _lib.HomanAmdError(f"observed-depth term: unsupported shape L={layers} B={batch}")
+        self.L, self.B = int(layers), int(batch)
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+class _DepthObsLoss(torch.autograd.Function):
+    """The observed-depth term (csrc/depthobs.hip; the rule is in include/homan_amd.h): one forward launch over all layers, which
+    also leaves the un-scaled clamped residuals; the backward scales them into the layers' gradient images in one launch."""
+
+    @staticmethod
+    def forward(ctx, depth_map, delta, scratch, sctxs, L, *images):
+        depths, sils, masks = images[:L], images[L:2 * L], images[2 * L:]
+        depths = [_lib.aligned(_f32(t), 16) for t in depths]
+        sils = [_lib.aligned(_f32(t), 16) for t in sils]
+        masks = [_lib.aligned(t.contiguous(), 4) for t in masks]
+        depth_map = _lib.aligned(_f32(depth_map), 16)
+        B, S = depths[0].shape[0], depths[0].shape[1]
+        for t in depths + sils + masks + [depth_map]:
+            assert tuple(t.shape) == (B, S, S), f"observed-depth term: image of shape {tuple(t.shape)}, expected {(B, S, S)}"
+        assert all(m.dtype == torch.uint8 for m in masks) and (scratch.L, scratch.B) == (L, B)
+        dev = depths[0].device
+        clamped = [torch.empty(B, S, S, device=dev) for _ in range(L)]
+        records = torch.empty(L, B, 2, device=dev)
+        out = torch.empty(4, device=dev)
+        p3 = lambda ts: [_lib.ptr(ts[i]) if i < L else None for i in range(3)]
+        _lib.check(_lib.lib().hm_depth_obs_fwd(*p3(depths), *p3(sils), *p3(masks), _lib.ptr(depth_map), L, B, S, float(delta),
+                                               NMR_NEAR, NMR_FAR, *p3(clamped), _lib.ptr(scratch.buf), _lib.ptr(records),
+                                               _lib.ptr(out), _lib.stream()), "hm_depth_obs_fwd")
+        ctx.save_for_backward(records, out, *clamped)
+        ctx.sctxs, ctx.L = sctxs, L
+        loss, stats = out[0].clone(), out[1:].clone()        # (stats: mean |r|, valid share, N - no gradient)
+        ctx.mark_non_differentiable(stats, records)
+        return loss, stats, records
+
+    @staticmethod
+    def backward(ctx, g_loss, *_unused):
+        records, out, *clamped = ctx.saved_tensors
+        L, (B, S) = ctx.L, clamped[0].shape[:2]
+        grads = [torch.empty_like(c) for c in clamped]
+        # the non-zero flags of hm_depth_bwd_sparse, when the caller named the renders' contexts (the masks cover a small part of
+        # the image) and the size has whole 64-pixel segments
+        flags = ([torch.empty(B * S * (S // 64), dtype=torch.uint8, device=records.device) for _ in range(L)]
+                 if ctx.sctxs is not None and S % 64 == 0 else [])
+        p3 = lambda ts: [_lib.ptr(ts[i]) if i < len(ts) else None for i in range(3)]
+        _lib.check(_lib.lib().hm_depth_obs_bwd(*p3(clamped), L, B, S, _lib.ptr(records), _lib.ptr(out),
+                                               _lib.ptr(_f32(g_loss).reshape(1)), *p3(grads), *p3(flags), _lib.stream()),
+                   "hm_depth_obs_bwd")
+        for sctx, g, f in zip(ctx.sctxs or [], grads, flags):
+            sctx.offer_gflags(g, f)
+        return (None, None, None, None, None) + tuple(grads) + (None,) * (2 * L)
+
+
+def depth_obs_loss(depths, sils, masks, depth_map, delta, scratch=None, sctxs=None, detail=False):
+    """The observed-depth term over 1..3 layers -> (0-d loss, mean |residual| over the valid pixels [m], valid pixels / mask
+    pixels with a usable sensor value); the two metrics carry no gradient.  depths / sils: the layers' (B,S,S) renders
+    (depth_render), masks: their (B,S,S) uint8 instance masks, depth_map (B,S,S) fp32 metres at the masks' resolution and in the
+    renders' camera (NaN, infinite, zero, negative and out-of-range values are ignored), 0 < delta <= 1 the Huber threshold [m].
+    scratch: a DepthObsScratch(L, B) kept by the caller (required under stream capture; else one is made for the call).
+    sctxs: the renders' SilhouetteContexts, ONLY when this term is the sole consumer of their depth images - their depth backward
+    then takes the sparse path on the flags this term's backward writes (image sizes that are multiples of 64).
+    detail=True appends (number of (layer, frame) with a valid pixel, records (L,B,2) = valid pixels, sum of rho)."""
+    L = len(depths)
+    if not (1 <= L <= 3 and len(sils) == L and len(masks) == L):
+        raise ValueError(f"observed-depth term: 1 to 3 layers with a silhouette and a mask each, got {L}/{len(sils)}/{len(masks)}")
+    if not 0 < float(delta) <= 1:
+        raise ValueError(f"observed-depth term: delta {delta} must lie in (0, 1] (metres)")
+    if sctxs is not None and len(sctxs) != L:
+        raise ValueError("observed-depth term: one raster context per layer")
+    if scratch is None:
+        scratch = DepthObsScratch(L, depths[0].shape[0], depths[0].device)
+    loss, stats, records = _DepthObsLoss.apply(depth_map, float(delta), scratch, sctxs, L, *depths, *sils, *masks)
+    return (loss, stats[0], stats[1]) + ((stats[2], records) if detail else ())
 
 
 # =============================================================================== shared small state

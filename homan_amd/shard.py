@@ -47,6 +47,9 @@ class ShardStepper:
         if float(loss_weights.get("lw_surf_attr", 0)) > 0 or float(loss_weights.get("lw_surf_rep", 0)) > 0:
             raise NotImplementedError("ShardStepper: the surface contact loss (lw_surf_attr / lw_surf_rep) is not covered by the "
                                       "fused loop (mode='graph' per clip)")
+        if float(loss_weights.get("lw_depth_obs", 0)) > 0:
+            raise NotImplementedError("ShardStepper: the observed-depth term (lw_depth_obs) is not covered by the fused loop "
+                                      "(mode='graph' per clip)")
         groups = OrderedDict()
         for i, mdl in enumerate(self.models):
             groups.setdefault(_shape_signature(mdl), []).append(i)
@@ -174,7 +177,7 @@ def _input_signature(kw, image_size, rend_size):
     faces = np.ascontiguousarray(torch.as_tensor(kw["faces_object"])[0].cpu().numpy())
     return (int(kw["translations_object"].shape[0]), int(kw["verts_object_og"].shape[1]), faces.shape[0], hash(faces.tobytes()),
             tuple(kw["hand_sides"]), int(kw["mano_pca_pose"].shape[1]), tuple(kw["target_masks_object"].shape[1:]),
-            tuple(kw["masks_object"].shape[-2:]), int(image_size), int(rend_size))
+            tuple(kw["masks_object"].shape[-2:]), int(image_size), int(rend_size), kw.get("depth_maps") is not None)
 
 
 class ClipFitter:
@@ -199,7 +202,9 @@ class ClipFitter:
     def __init__(self, loss_weights, num_iterations=400, lr=1e-2, clips_per_batch=1, max_resident=4, class_name="default",
                  hand_proj_mode="persp", optimize_mano=True, optimize_mano_beta=True, optimize_object_scale=False,
                  image_size=640, mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4,
-                 surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all"):
+                 surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all",
+                 depth_obs_delta=0.03, depth_obs_layers="all"):
+        # (the observed-depth term's maps are a clip's own data: clip["depth_maps"], beside clip["camintr"])
         self.lw, self.steps, self.lr = dict(loss_weights), int(num_iterations), float(lr)
         self.cpb, self.max_resident = max(1, int(clips_per_batch)), max(1, int(max_resident))
         self.model_kw = dict(class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode, optimize_mano=optimize_mano,
@@ -207,8 +212,9 @@ class ClipFitter:
                              image_size=image_size, mano_model=mano_model, rend_size=rend_size, sync_metrics=False,
                              ordinal_depth=ordinal_depth, sil_mode=sil_mode, sil_sigma=sil_sigma,
                              surface_contact_thresh=surface_contact_thresh, surface_collision_thresh=surface_collision_thresh,
-                             surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones)
-        self.resident = OrderedDict()          # (signature, clips) -> FusedStepper
+                             surface_two_way=surface_two_way, surface_contact_zones=surface_contact_zones,
+                             depth_obs_delta=depth_obs_delta, depth_obs_layers=depth_obs_layers)
+        self.resident = OrderedDict()         # (signature, clips) -> FusedStepper
         self._one_by_one = set()          # shape signatures whose clips the fused loop takes one at a time
         self._graph_only = set()          # ... and those it refuses altogether (ortho, free hand scale): the autograd hipGraph
         self.resident_graph = OrderedDict()    # signature -> GraphStepper (one per shape, reloaded per clip)
@@ -222,6 +228,8 @@ class ClipFitter:
     def _inputs(self, clip):
         kw = collate_inputs(clip["person_parameters"], clip["object_parameters"], clip["objvertices"], clip["objfaces"])
         kw["camintr"] = clip.get("camintr")
+        if clip.get("depth_maps") is not None:        # (the observed-depth term: a clip's own maps, beside its camintr)
+            kw["depth_maps"] = clip["depth_maps"]
         return kw
 
     def fit(self, clips):

@@ -741,6 +741,48 @@ int hm_surface_contact_bwd(const float* unit_points, const int* inside, const fl
                            const float* unit_verts_rep, const float* upstream, long n_points, long n_verts, float* grad_points,
                            float* grad_verts, hipStream_t stream);
 
+/* ------------------------------------------------------------------ observed-depth term (csrc/depthobs.hip)
+ * The rendered depth of every layer against a sensor depth map registered with the instance masks.  Not in the reference tree:
+ * the rule below IS the definition, pinned bit for bit by the fp32 NumPy restatement of
+ * tests/depthobs_ref.py.  Every fp32 operation is IEEE without contraction.
+ *
+ * L = 1..3 layers; d_l / a_l: depth / silhouette renders (B,S,S) f32; m_l: instance masks (B,S,S) u8; depth_map D (B,S,S) f32,
+ * metres, in the camera of the renders.  Pointers of layers >= L are not read (NULL).  Pixel p of frame b is VALID for layer l iff
+ *   znear <= D[b,p] <= zfar (false for NaN, +-inf, negative and zero values)  and  m_l[b,p] != 0  and  a_l[b,p] == 1.0f
+ *   and  0 <= d_l[b,p] <= zfar (a guard: the rasteriser's depth of a fully covered pixel always is).
+ * For a valid pixel r = d_l - D, ar = |r|, rho = ar <= delta ? (0.5f * r) * r : delta * (ar - 0.5f * delta),
+ * c_l[b,p] = min(max(r, -delta), delta); c_l = 0 exactly on every other pixel (written in full).
+ * Sums are exact: rho and ar are rounded to the grid 2^-32 (in double, round to nearest even) and added as 64-bit integer counts
+ * of quanta; with delta <= 1 and zfar <= 100 a frame of 1024^2 pixels stays below 2^59 quanta.  No floating-point atomics; two
+ * calls return the same bits, a frame's record and images do not depend on its place in the batch, and the clip's values do not
+ * depend on the order of the frames.
+ *   records (L,B,2) f32: n[l,b] = valid pixels (exact), (float)((double)Q[l,b] / 2^32) with Q the quanta of sum rho;
+ *   N = number of (l,b) with n > 0;  M[l,b] = rint((double)Q / (double)n) (the record's mean, in quanta; double division);
+ *   out4[0] = loss = N ? (float)(((double)sum M / 2^32) / (double)N) : 0;
+ *   out4[1] = mean |r| over all valid pixels = (float)((((double)hi * 2^32 + (double)lo) / 2^32) / (double)sum n), hi / lo the
+ *             sums of the upper / lower 32 bits of the records' |r| quanta; 0 without a valid pixel;
+ *   out4[2] = sum n / (pixels with m_l != 0 and a usable D, over all layers), in double, rounded to fp32; 0 when there are none;
+ *   out4[3] = N.
+ * frame_acc: hm_depth_obs_acc_bytes(L, B) bytes, ZERO-filled once by the caller; the call leaves it zero again (the records'
+ * integer words and the ticket of the finishing workgroup).  One launch, nothing allocated or synchronised, no host read: the
+ * call can be captured in a hipGraph.
+ * hm_depth_obs_bwd (the forward writes the un-scaled c_l, the backward only scales them): upstream (1) fp32 on the device,
+ *   g_l[b,p] = c_l[b,p] * w[l,b] with w = (upstream[0] / N) / n[l,b] in fp32, exactly 0 where c_l is 0 or n[l,b] = 0.
+ * flags0..2 (for every layer or for none; S % 64 == 0): B * S * (S / 64) bytes per layer, 1 where some pixel of the 64-pixel
+ * row segment has a non-zero g_l, else 0 - the `gflags` of hm_depth_bwd_sparse.
+ * HM_ERR_BAD_ARG before any HIP call: L outside 1..3, B < 1, S < 1 or S > 1024, delta outside (0, 1], not 0 < znear < zfar <= 100,
+ * a NULL buffer of a layer < L, a misaligned pointer.
+ * ALIGNMENT: frame_acc 8 bytes.  When S * S is a multiple of 4 (every even S; the rasteriser's sizes are multiples of 16) the
+ * kernels move four pixels at a time: d_l, a_l, c_l, g_l and depth_map 16 bytes, m_l 4 bytes.  Other S: element alignment. */
+size_t hm_depth_obs_acc_bytes(int L, int B);
+int hm_depth_obs_fwd(const float* d0, const float* d1, const float* d2, const float* a0, const float* a1, const float* a2,
+                     const unsigned char* m0, const unsigned char* m1, const unsigned char* m2, const float* depth_map, int L,
+                     int B, int S, float delta, float znear, float zfar, float* c0, float* c1, float* c2, void* frame_acc,
+                     float* records, float* out4, hipStream_t stream);
+int hm_depth_obs_bwd(const float* c0, const float* c1, const float* c2, int L, int B, int S, const float* records,
+                     const float* out4, const float* upstream, float* g0, float* g1, float* g2, unsigned char* flags0,
+                     unsigned char* flags1, unsigned char* flags2, hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
