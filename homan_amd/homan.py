@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import constants, lossutils, nmr, ops, trans3d
+from .depthprep import SensorDepth
 from .losses import Losses
 from .manomodel import ManoModel
 from .meshutils import get_faces_and_textures
@@ -61,9 +62,10 @@ def clip_tensors(translations_object, rotations_object, verts_object_og, transla
     device; with it, what is DERIVED (mask comparisons, constants) is formed there - the clip's own arrays stay where the
     caller has them, so that the consumer's copy is their one transfer.
     depth_maps (optional, a homan_amd extra: the observed-depth term): (B, S, S) sensor depth in METRES, in
-    the camera of `camintr` and registered pixel for pixel with the instance masks, i.e. at THEIR resolution - bringing raw sensor
-    frames (another resolution, millimetres, uint16) to that grid is the caller's job.  NaN, infinite, zero, negative and
-    out-of-range values mark pixels without a measurement.  Adds the buffer `depth_maps`."""
+    the camera of `camintr` and registered pixel for pixel with the instance masks, i.e. at THEIR resolution - raw sensor frames
+    (another resolution, millimetres, uint16, a depth camera of its own) are brought to that grid by depthprep.prepare_depth_maps,
+    or handed to HOMan / load_clip as a depthprep.SensorDepth, which they prepare with their own camintr before this function.
+    NaN, infinite, zero, negative and out-of-range values mark pixels without a measurement.  Adds the buffer `depth_maps`."""
     f32 = lambda t: torch.as_tensor(t).detach().float()
     rot6d = lambda r: (matrix_to_rot6d(r) if r.shape[-1] == 3 else r).contiguous()
     const = lambda shape, value: torch.full(tuple(shape), float(value), device=device)
@@ -124,7 +126,9 @@ class HOMan(nn.Module):
             raise ValueError(f"depth_obs_layers {depth_obs_layers} not in [all|object|hand]")
         if not 0 < float(depth_obs_delta) <= 1:
             raise ValueError(f"depth_obs_delta {depth_obs_delta} must lie in (0, 1] (metres; the kernel's exact sums are sized for it)")
-        if depth_maps is not None:
+        if isinstance(depth_maps, SensorDepth):           # (raw sensor frames: registered below, against THIS model's camera)
+            depth_maps.check(translations_object.shape[0], image_size)
+        elif depth_maps is not None:
             want = (translations_object.shape[0], int(image_size), int(image_size))
             if tuple(torch.as_tensor(depth_maps).shape) != want:
                 raise ValueError(f"depth_maps of shape {tuple(torch.as_tensor(depth_maps).shape)}: expected (B, image_size, "
@@ -145,6 +149,8 @@ class HOMan(nn.Module):
         if not torch.cuda.is_available():
             raise RuntimeError("homan_amd.HOMan needs an MI355X (ROCm) device; there is no CPU path")
         dev = torch.device("cuda")
+        if isinstance(depth_maps, SensorDepth):
+            depth_maps = depth_maps.prepare(camintr, int(image_size))
         self.hand_proj_mode = hand_proj_mode
         self.hand_sides = hand_sides
         self.hand_nb = len(hand_sides)
@@ -246,6 +252,9 @@ class HOMan(nn.Module):
             raise ValueError("load_clip: other hand sides")
         if faces_object is not None and not torch.equal(torch.as_tensor(faces_object)[0].cpu(), self.faces_object[0].cpu()):
             raise ValueError("load_clip: other object topology")
+        if isinstance(clip.get("depth_maps"), SensorDepth):
+            clip["depth_maps"].check(torch.as_tensor(clip["translations_object"]).shape[0], self.image_size)
+            clip = dict(clip, depth_maps=clip["depth_maps"].prepare(clip.get("camintr"), int(self.image_size)))
         new = clip_tensors(**dict(clip, hand_proj_mode=self.hand_proj_mode, device=self.translations_object.device))
         if hasattr(self, "depth_maps") and "depth_maps" not in new:
             raise ValueError("load_clip: the model was built with depth_maps; every later clip must bring depth_maps too")

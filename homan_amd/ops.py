@@ -660,6 +660,35 @@ def depth_obs_loss(depths, sils, masks, depth_map, delta, scratch=None, sctxs=No
     return (loss, stats[0], stats[1]) + ((stats[2], records) if detail else ())
 
 
+def register_depth(frames, depth_scale, Kd, T, Kc, size, znear=NMR_NEAR, zfar=NMR_FAR, edge_radius=1, edge_jump_abs=0.02,
+                   edge_jump_rel=0.0, max_splat=8, out=None, stats=None):
+    """hm_depth_register (csrc/depthprep.hip; the rule is in include/homan_amd.h): raw sensor frames (B,Hd,Wd), uint16 or fp32
+    device tensor, -> ((B,size,size) fp32 metres in the colour camera with 0 = no measurement, stats (B,4) int32 = valid source
+    pixels, dropped by the edge filter, dropped by the range / splat rules, valid target pixels).  Kd (3,3) or (B,3,3) pixel
+    intrinsics of the depth camera, T (3,4) or (B,3,4) depth -> colour, Kc (3,3) or (B,3,3) normalised `camintr`: fp32 device
+    tensors.  Three launches on the current stream, nothing else: with `out` / `stats` given the call can be captured."""
+    if frames.dtype not in (torch.uint16, torch.float32) or frames.dim() != 3:
+        raise ValueError(f"register_depth: frames must be (B, Hd, Wd) uint16 or float32, got {tuple(frames.shape)} {frames.dtype}")
+    B, Hd, Wd = frames.shape
+    mats = []
+    for name, m, shape in (("Kd", Kd, (3, 3)), ("T", T, (3, 4)), ("Kc", Kc, (3, 3))):
+        if m.dtype != torch.float32 or tuple(m.shape) not in (shape, (B,) + shape):
+            raise ValueError(f"register_depth: {name} must be fp32 {shape} or {(B,) + shape}, got {tuple(m.shape)} {m.dtype}")
+        mats.append((m.contiguous(), int(m.dim() == 3)))
+    size = int(size)
+    frames = frames.contiguous()
+    out = torch.empty(B, size, size, dtype=torch.float32, device=frames.device) if out is None else out
+    stats = torch.empty(B, 4, dtype=torch.int32, device=frames.device) if stats is None else stats
+    assert tuple(out.shape) == (B, size, size) and out.dtype == torch.float32 and tuple(stats.shape) == (B, 4)
+    assert stats.dtype == torch.int32
+    (kd, kd_s), (t, t_s), (kc, kc_s) = mats
+    _lib.check(_lib.lib().hm_depth_register(_lib.ptr(frames), int(frames.dtype == torch.float32), B, Hd, Wd, float(depth_scale),
+                                            _lib.ptr(kd), kd_s, _lib.ptr(t), t_s, _lib.ptr(kc), kc_s, size, float(znear),
+                                            float(zfar), int(edge_radius), float(edge_jump_abs), float(edge_jump_rel),
+                                            int(max_splat), _lib.ptr(out), _lib.ptr(stats), _lib.stream()), "hm_depth_register")
+    return out, stats
+
+
 # =============================================================================== shared small state
 class ReduceWorkspace:
     """Zero-initialised scratch for the single-launch grid reductions (partials + self-resetting ticket)."""

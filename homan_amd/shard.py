@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .depthprep import clip_sensor_depth
 from .homan import HOMan
 from .fused import FusedStepper
 from .loopcommon import collate_inputs
@@ -204,7 +205,8 @@ class ClipFitter:
                  image_size=640, mano_model=None, rend_size=256, ordinal_depth=False, sil_mode="nmr", sil_sigma=1e-4,
                  surface_contact_thresh=0.010, surface_collision_thresh=0.020, surface_two_way=False, surface_contact_zones="all",
                  depth_obs_delta=0.03, depth_obs_layers="all"):
-        # (the observed-depth term's maps are a clip's own data: clip["depth_maps"], beside clip["camintr"])
+        # (the observed-depth term's maps are a clip's own data: clip["depth_maps"], beside clip["camintr"] - or raw sensor frames,
+        #  clip["depth_frames"] with clip["depth_camintr"] [, "depth_to_color", "depth_scale", "depth_options"]: depthprep)
         self.lw, self.steps, self.lr = dict(loss_weights), int(num_iterations), float(lr)
         self.cpb, self.max_resident = max(1, int(clips_per_batch)), max(1, int(max_resident))
         self.model_kw = dict(class_name=class_name, int_scale_init=1, hand_proj_mode=hand_proj_mode, optimize_mano=optimize_mano,
@@ -226,9 +228,16 @@ class ClipFitter:
         return time.perf_counter()
 
     def _inputs(self, clip):
+        # (raw sensor frames, clip["depth_frames"] with clip["depth_camintr"]: refused beside clip["depth_maps"] before any copy)
+        sensor = clip_sensor_depth(clip)
         kw = collate_inputs(clip["person_parameters"], clip["object_parameters"], clip["objvertices"], clip["objfaces"])
         kw["camintr"] = clip.get("camintr")
-        if clip.get("depth_maps") is not None:        # (the observed-depth term: a clip's own maps, beside its camintr)
+        if sensor is not None:
+            # registered on the device against the clip's own camintr, at the fitter's image size: from here on the clip is one
+            # that brings maps (same shape signature, same resident stepper)
+            sensor.check(kw["translations_object"].shape[0], self.model_kw["image_size"])
+            kw["depth_maps"] = sensor.prepare(kw["camintr"], int(self.model_kw["image_size"]))
+        elif clip.get("depth_maps") is not None:        # (the observed-depth term: a clip's own maps, beside its camintr)
             kw["depth_maps"] = clip["depth_maps"]
         return kw
 

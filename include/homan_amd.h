@@ -783,6 +783,51 @@ int hm_depth_obs_bwd(const float* c0, const float* c1, const float* c2, int L, i
                      const float* out4, const float* upstream, float* g0, float* g1, float* g2, unsigned char* flags0,
                      unsigned char* flags1, unsigned char* flags2, hipStream_t stream);
 
+/* ------------------------------------------------------------------ sensor depth onto the fit's pixel grid (csrc/depthprep.hip)
+ * Raw depth frames of a sensor - its own resolution, units and camera - registered into the `depth_map` of hm_depth_obs_fwd:
+ * (B,S,S) fp32 metres in the colour camera, exactly 0.0f where nothing was measured.  Not in the reference tree: the rule below
+ * IS the definition, pinned bit for bit by the fp32 NumPy restatement of tests/depthprep_ref.py.  Every
+ * fp32 operation is IEEE (division included), one rounding each, in the order written, without contraction.
+ *
+ * frames (B,Hd,Wd): uint16 (frames_f32 == 0) or fp32 (!= 0), a typed void pointer.  Kd, T, Kc: DEVICE arrays, row-major, read
+ * by the kernel: Kd (3,3) the depth camera's PIXEL intrinsics, of which fxd = Kd[0], cxd = Kd[2], fyd = Kd[4], cyd = Kd[5] are
+ * read (no skew); T (3,4) the rigid transform depth camera -> colour camera, t0..t11; Kc (3,3) the colour camera NORMALISED by
+ * the image size as HOMan's `camintr`, of which Kc[0], Kc[2], Kc[4], Kc[5] are read.  *_stride is 0 (one matrix for every frame)
+ * or 1 (frame b reads matrix b).  The matrices are not inspected on the host (the call reads nothing there); a non-finite entry
+ * only ever drops pixels (every comparison below is false for a NaN).
+ * Source validity: z = (float)raw * depth_scale; valid iff znear <= z <= zfar (false for NaN, +-inf, zero, negative values).
+ * Edge filter (r = edge_radius, 0 = off): a valid source pixel is dropped if some VALID pixel zn of its (2r+1)^2 window inside
+ *   the frame has |zn - z| > (edge_jump_rel * z) + edge_jump_abs.
+ * Footprint of a surviving pixel (row v, column u), which covers [u, u+1) x [v, v+1): with S_f = (float)S,
+ *   Fx = Kc[0] * S_f, Cx = Kc[2] * S_f, Fy = Kc[4] * S_f, Cy = Kc[5] * S_f;
+ *   for (p, q) in {(u, v), (u + 1, v + 1), (u + 0.5, v + 0.5)} (exact in fp32):
+ *     X = ((p - cxd) / fxd) * z,  Y = ((q - cyd) / fyd) * z,
+ *     Xc = ((t0 * X + t1 * Y) + t2 * z) + t3,  Yc = ((t4 * X + t5 * Y) + t6 * z) + t7,  Zc = ((t8 * X + t9 * Y) + t10 * z) + t11;
+ *   zc = Zc of the centre.  Dropped unless znear <= zc <= zfar and Zc >= znear at both corners.
+ *   px = (Xc / Zc) * Fx + Cx, py = (Yc / Zc) * Fy + Cy at the two corners; dropped unless all four are within +-2^24.
+ *   xa = min(px0, px1), xb = max(px0, px1) (a mirroring transform swaps the ends), likewise ya, yb.  The pixel covers the target
+ *   pixels (row, col) whose CENTRE (col + 0.5, row + 0.5) lies in [xa, xb) x [ya, yb):
+ *     c0 = max(ceil(xa - 0.5f), 0), c1 = min(ceil(xb - 0.5f), S), col in [c0, c1); rows likewise (clipped to the image).
+ *   An empty range writes nothing.  c1 - c0 > max_splat or r1 - r0 > max_splat: the pixel is dropped and counted, not clamped.
+ *   Target (row, col) is the pixel ops.depth_render calls (row, col) at size S under the same Kc.
+ * Merge: a target pixel keeps the MINIMUM zc it received - an unsigned-integer atomicMin on the bit patterns (zc > 0) straight
+ * into `out`, pre-filled with the pattern of +inf; the finish turns what is left of it into 0.0f.  No floating-point atomics: the
+ * same bits on every run, at any place in the batch.
+ * stats (B,4) int32, by integer adds: valid source pixels, dropped by the edge filter, dropped by the range / projection / splat
+ * rules, valid target pixels.
+ * Three launches (fill, splat, finish) on `stream`; nothing allocated or synchronised, no host read: capturable in a hipGraph.
+ * `out` is the only scratch.
+ * HM_ERR_BAD_ARG before any HIP call: a NULL pointer; B, Hd, Wd or S < 1; S > 1024 (the depth term's limit); B > 65535;
+ * edge_radius outside 0..3; max_splat < 1; depth_scale not positive and finite; not 0 < znear < zfar <= 100; a negative or
+ * non-finite edge_jump_abs / edge_jump_rel; a stride other than 0 or 1; a misaligned pointer.
+ * ALIGNMENT: frames to its element (2 bytes uint16, 4 bytes fp32); out 16 bytes when S * S is a multiple of 4 (four pixels per
+ * lane in fill and finish), else 4.  Source rows are read 16 bytes per lane where `frames` is 16-byte aligned and Wd is a multiple
+ * of 8 (uint16) or 4 (fp32), element by element otherwise: the result is the same. */
+int hm_depth_register(const void* frames, int frames_f32, int B, int Hd, int Wd, float depth_scale, const float* Kd, int Kd_stride,
+                      const float* T, int T_stride, const float* Kc, int Kc_stride, int S, float znear, float zfar,
+                      int edge_radius, float edge_jump_abs, float edge_jump_rel, int max_splat, float* out, int* stats,
+                      hipStream_t stream);
+
 /* ------------------------------------------------------------------ mask crops and target masks
  * detectron2 `BitMasks(masks).crop_and_resize(boxes, S)` as called at reference homan/lib2d/maskutils.py:29-30 and :61-64
  * and homan/prepare/gtmasks.py:87-101: ROIAlign (output (S,S), spatial_scale 1, sampling_ratio 0, aligned) of the mask
