@@ -217,12 +217,25 @@ __global__ __launch_bounds__(1024) void k_rigid_bwd(const float* __restrict__ me
 // The object's rigid backward of the fused loops (exact sums, silhouette gather): one workgroup of up to 1024 threads per
 // (frame, chunk of 1024 * NV vertices), every thread NV vertices whose dependent loads - CSR offsets -> corner items ->
 // per-corner sums - are issued STAGE BY STAGE for all NV at once: the kernel is a chain of round trips on the tail of the
-// iteration, and a loop over a thread's vertices walked that chain once per vertex.  Meshes of <= 1024 * NV vertices (the
-// 1502-vertex bottle at NV = 2) are one workgroup per frame: no chunk records, no ticket, no second round trip.
+// iteration, and a loop over a thread's vertices walked that chain once per vertex.  A frame of one chunk has no records, no
+// ticket and no second round trip.  A frame of several (the launcher's choice, see rigid_bwd_launch) combines them in wave 0
+// of the last workgroup to arrive, without a barrier: 13 lanes store the chunk's record in one instruction, lane 0 draws the
+// ticket, 13 lanes reload and add the frame's records side by side; the frame's rot6d is in registers since the first line.
 // Optional temporal-smoothness term of the SAME vertices (reference homan/lossutils.py:18-36), formed here from the
 // camera-space vertices of the neighbouring frames with the arithmetic of smooth_body (pair_bodies.h): the object's chain then
 // waits for nothing the hand-side stream produces.  It is added FIRST, like the first entry of `terms` used to be.
 struct SmoothIn { const float* verts; float w; };
+#define RIGID_MAX_CHUNKS 16
+#ifdef HM_CHAIN_STAMPS      // phases of the critical workgroup (hm_common.h HM_PH; tools/tail_phases.py)
+static __device__ unsigned long long g_tail_ph[16];
+#define RPH_DECL() HM_PH_DECL()
+#define RPH(k) HM_PH(k)
+#define RPH_FLUSH() HM_PH_FLUSH(g_tail_ph)
+#else
+#define RPH_DECL()
+#define RPH(k)
+#define RPH_FLUSH()
+#endif
 template <int NV, int MAXT>
 __global__ __launch_bounds__(MAXT) void k_rigid_bwd_x(const float* __restrict__ mesh, const float* __restrict__ rot6d,
                                                      const float* __restrict__ scale, int abs_scale, RigidTerms terms,
@@ -233,11 +246,14 @@ __global__ __launch_bounds__(MAXT) void k_rigid_bwd_x(const float* __restrict__ 
 {
     HM_LATENCY_KERNEL();
     HM_STAMP_START(1);
+    RPH_DECL();
+    RPH(0);
     __shared__ double red13d[16 * 13];
-    __shared__ int s_flag;
     const int n = blockIdx.x;
-    float R[9];
-    rot6d_to_mat(rot6d + n * 6, R);
+    float r6[6], R[9];              // the frame's rot6d stays in registers: rot6d_backward at the very end asks memory for nothing
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r6[k] = rot6d[n * 6 + k];
+    rot6d_to_mat(r6, R);
     const float sraw = scale[n / clip_len];
     const float s = abs_scale ? fabsf(sraw) : sraw;
     const int fl = n % clip_len;                                    // frame inside its clip (smoothness: no term across clips)
@@ -277,12 +293,14 @@ __global__ __launch_bounds__(MAXT) void k_rigid_bwd_x(const float* __restrict__ 
     for (int j = 0; j < NV; ++j)
 #pragma unroll
         for (int c = 0; c < 3; ++c) sv[j][c] = sm.verts ? sm.verts[((long)n * V + (ok[j] ? vv[j] : 0)) * 3 + c] : 0.f;
+    RPH(1);
     // ---- stage B: the first eight corner items of every vertex; stage C: their per-corner sums
     int item[NV][8];
 #pragma unroll
     for (int j = 0; j < NV; ++j)
 #pragma unroll
         for (int k = 0; k < 8; ++k) item[j][k] = (ok[j] && a0[j] + k < a1[j]) ? sil.adj_items[a0[j] + k] : -1;
+    RPH(2);
     double su[NV], sw[NV];
     {
         const double2* pf = reinterpret_cast<const double2*>(sil.parts + (long)n * sil.F * 6);
@@ -302,6 +320,7 @@ __global__ __launch_bounds__(MAXT) void k_rigid_bwd_x(const float* __restrict__ 
             }
         }
     }
+    RPH(3);
     double accd[13];
 #pragma unroll
     for (int k = 0; k < 13; ++k) accd[k] = 0.0;
@@ -347,36 +366,58 @@ __global__ __launch_bounds__(MAXT) void k_rigid_bwd_x(const float* __restrict__ 
         accd[12] += hm_quant(m[j][0] * dm[0] + m[j][1] * dm[1] + m[j][2] * dm[2], magic);
     }
     hm_block_sum_n_f64<13>(accd, red13d);
+    RPH(4);
+    // every thread holds the workgroup's 13 sums now, and wave 0 alone finishes: no barrier and no LDS word from here on
+    if (threadIdx.x >= HM_WAVE) return;
     if (gridDim.y > 1) {
-        double* rec = reinterpret_cast<double*>(partials + ((long)n * gridDim.y + blockIdx.y) * 32);
+        // chunk record of 13 doubles (32 floats apart): ONE agent-scope store instruction, lane k its value k
+        double mine = 0.0;
+#pragma unroll
+        for (int k = 0; k < 13; ++k) mine = (int)threadIdx.x == k ? accd[k] : mine;
+        if (threadIdx.x < 13)
+            __hip_atomic_store(reinterpret_cast<double*>(partials + ((long)n * gridDim.y + blockIdx.y) * 32) + threadIdx.x, mine,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        RPH(5);
+        // last-arriver ticket as in hm_last_block (the wave's record stores have landed before lane 0 draws it; the last one
+        // re-arms the word), handed to the wave's lanes through a scalar register
+        unsigned int ticket = 0;
         if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < 13; ++k) __hip_atomic_store(rec + k, accd[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ticket = atomicAdd(frame_cnt + n, 1u);
+            if (ticket == gridDim.y - 1u) atomicExch(frame_cnt + n, 0u);
         }
-        if (!hm_last_block(frame_cnt + n, gridDim.y, &s_flag)) return;
-        if (threadIdx.x < 13 * gridDim.y)
-            red13d[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const double*>(partials + ((long)n * gridDim.y + threadIdx.x / 13) * 32) + threadIdx.x % 13,
-                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (threadIdx.x == 0) {
+        ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
+        asm volatile("" ::: "memory");          // (no record load moves in front of the ticket)
+        RPH(6);
+        if (ticket != gridDim.y - 1u) { RPH_FLUSH(); return; }
+        // the frame's records: lane k requests value k of every chunk together (<= 16 loads in flight, one round trip) and adds
+        // them - 13 parallel chains instead of one thread's 13 x chunks adds; the sums are exact, their order is immaterial
+        double part[RIGID_MAX_CHUNKS];
+        const double* recs = reinterpret_cast<const double*>(partials + (long)n * gridDim.y * 32) + (threadIdx.x < 13 ? threadIdx.x : 0);
 #pragma unroll
-            for (int k = 0; k < 13; ++k) accd[k] = 0.0;
-            for (unsigned c = 0; c < gridDim.y; ++c)
+        for (int c = 0; c < RIGID_MAX_CHUNKS; ++c)
+            part[c] = c < (int)gridDim.y ? __hip_atomic_load(recs + c * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        mine = 0.0;
 #pragma unroll
-                for (int k = 0; k < 13; ++k) accd[k] += red13d[c * 13 + k];
-        }
+        for (int c = 0; c < RIGID_MAX_CHUNKS; ++c) mine += part[c];
+        RPH(7);
+#pragma unroll
+        for (int k = 0; k < 13; ++k)
+            accd[k] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mine), k), __builtin_amdgcn_readlane(__double2loint(mine), k));
     }
     if (threadIdx.x == 0) {
         float tot[13], dr6[6];
 #pragma unroll
         for (int k = 0; k < 13; ++k) tot[k] = (float)accd[k];
-        rot6d_backward(rot6d + n * 6, tot, dr6);
+        rot6d_backward(r6, tot, dr6);
 #pragma unroll
         for (int k = 0; k < 6; ++k) g_rot6d[n * 6 + k] = dr6[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) g_trans[n * 3 + k] = tot[9 + k];
         if (g_scale_part) g_scale_part[n] = (abs_scale && sraw < 0.f) ? -tot[12] : tot[12];
     }
+    RPH(8);
+    RPH_FLUSH();
     HM_STAMP_END(1);
 }
 
@@ -420,7 +461,6 @@ int hm_rigid_fwd(const float* mesh, const float* rot6d, const float* trans, cons
 {
     return hm_rigid_fwd_clips(mesh, rot6d, trans, scale, abs_scale, N, V, rotmat, verts, 0, stream);
 }
-#define RIGID_MAX_CHUNKS 16
 size_t hm_rigid_workspace_bytes(int N) { return (((size_t)N * 4 + 255) & ~(size_t)255) + (size_t)N * RIGID_MAX_CHUNKS * 32 * 4; }
 static int rigid_bwd_launch(const float* mesh, const float* rot6d, const float* scale, int abs_scale,
                             const float* const* g_terms, const float* weights, int n_terms, SilGather sil,
@@ -444,9 +484,13 @@ static int rigid_bwd_launch(const float* mesh, const float* rot6d, const float* 
     unsigned int* cnt = (unsigned int*)workspace;
     float* partials = workspace ? (float*)((char*)workspace + (((size_t)N * 4 + 255) & ~(size_t)255)) : nullptr;
     // meshes of up to 16 chunks of 256 vertices: ceil(V / 256) workgroups of 256 threads per frame, one vertex per thread
-    // (same-box A/B, cfg2: 6295 it/s against 6110 with one 768-thread workgroup per frame; the sums are exact, results do not
-    // depend on the split).  Larger meshes: 768 threads x 2 vertices per chunk, up to 24 576 vertices (12 waves: 170 registers
-    // each, the 64 of the staged double2 loads included - at 1024 threads the 128-register cap spilled)
+    // (the sums are exact, results do not depend on the split).  The other design - the 1502-vertex bottle as ONE 768-thread
+    // workgroup of two vertices per thread per frame, no records and no ticket - was measured again with the staged loads and
+    // the wave-level combine, alternated on one box, plain benchmark, three runs each: 6 548 / 6 520 / 6 521 it/s against
+    // 6 873 / 6 856 / 6 837 for the chunks (EXPERIMENTS.md, "Iteration tail"): a twelve-wave workgroup's barriers and two
+    // passes of the load chain per thread cost more than the combine.  Larger meshes: 768 threads x 2 vertices per chunk, up to
+    // 24 576 vertices (12 waves: 170 registers each, the 64 of the staged double2 loads included - at 1024 threads the
+    // 128-register cap spilled)
     const bool small = V <= RIGID_MAX_CHUNKS * 256;
     const int nv = small ? 1 : 2;
     const int thr = small ? 256 : 768;
@@ -535,6 +579,15 @@ int hm_debug_chain_geometry(unsigned long long* out, int reset)
     (void)hipDeviceSynchronize();
     if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chain_ts), sizeof(z));
     if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain_ts), z, sizeof(z));
+    return HM_OK;
+}
+int hm_debug_tail_geometry(unsigned long long* out, int reset)          // k_rigid_bwd_x: 15 phase maxima, first start in [15]
+{
+    unsigned long long z[16] = {0};
+    z[15] = ~0ull;
+    (void)hipDeviceSynchronize();
+    if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_ph), sizeof(z));
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tail_ph), z, sizeof(z));
     return HM_OK;
 }
 #endif

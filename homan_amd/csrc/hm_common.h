@@ -21,6 +21,16 @@ static __device__ unsigned long long g_chain_ts[8];
 #define HM_STAMP_START(k)
 #define HM_STAMP_END(k)
 #endif
+// Phase stamps of the iteration's two tail kernels (k_rigid_bwd_x: -DHM_CHAIN_STAMPS, k_mano_bwd: -DMANO_PHASES; tools/
+// tail_phases.py).  Thread 0 keeps the wall clock of every mark in registers - taken once everything requested before the mark
+// has landed - and leaves, when its workgroup is done, the per-phase MAXIMUM over the launch's workgroups (the critical workgroup
+// is the last to reach a phase) and in slot 15 the launch's first start.  The release build carries none of it.
+#if defined(HM_CHAIN_STAMPS) || defined(MANO_PHASES)
+#define HM_PH_DECL() unsigned long long ph_[15] = {}
+#define HM_PH(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ph_[k] = wall_clock64(); } while (0)
+#define HM_PH_FLUSH(arr) do { if (threadIdx.x == 0) { atomicMin(&(arr)[15], ph_[0]); \
+        for (int k_ = 0; k_ < 15; ++k_) if (ph_[k_]) atomicMax(&(arr)[k_], ph_[k_]); } } while (0)
+#endif
 // the kernels of the hand-side chain that are long enough to matter to whatever they overlap (MANO backward, pair terms),
 // and the three heavy kernels of the silhouette chain: separately tunable (A/B builds)
 #ifndef HM_HAND_PRIO
@@ -165,8 +175,11 @@ __device__ __forceinline__ float hm_block_max(float v, float* red)
 // line of the L2 (buffer_wbl2), once per workgroup, while the rasteriser next door is filling that L2 with its own
 // output (measured: the small reductions and the rasteriser both ran ~1.7x slower when overlapped).  Instead the
 // records themselves travel at agent scope: hm_partial_store (write-through, sc1) by the producer, s_waitcnt vmcnt(0)
-// before the ticket, hm_partial_load (sc1, never served from a stale L2 line) by the finishing block.  Records MUST be
-// written with hm_partial_store by the thread that calls the ticket (thread 0) and read with hm_partial_load.
+// before the ticket, hm_partial_load (sc1, never served from a stale L2 line) by the finishing block.  With hm_last_block
+// the records MUST be written with hm_partial_store by the thread that draws the ticket (thread 0: its s_waitcnt covers its own
+// wave's stores only) and read with hm_partial_load.  Two kernels keep the same protocol in another shape: k_mano_bwd
+// (mano.hip) lets every thread store, each wave waits for its own stores (s_waitcnt vmcnt(0)) and a barrier stands in front
+// of thread 0's ticket; k_rigid_bwd_x (geometry.hip) stores, waits, draws and reloads inside wave 0, with no barrier at all.
 // `counter` must be zero on entry; the last block resets it, so one zero-initialised word serves every launch on the
 // stream.
 // Usage:   if (hm_last_block(counter, nblocks, &s_flag)) { ...read partials, write result... }

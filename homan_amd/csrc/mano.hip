@@ -215,6 +215,23 @@ __device__ __forceinline__ void mano_posed_chunk(const ManoModelDev& m, const Ma
     __syncthreads();
 }
 
+// T = sum_j W[v][j] A[j] from the vertex's row of weights, four float4 (the caller has it in registers)
+__device__ __forceinline__ void mano_skin_transform_w(const ManoShared& sh, const float4* wrow, float* T)
+{
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 w4 = wrow[q];
+        const float ws[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = 4 * q + u;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] += ws[u] * sh.A[j][k];
+        }
+    }
+}
 __device__ __forceinline__ void mano_skin_transform(const ManoModelDev& m, const ManoShared& sh, int v, float* T)
 {
 #pragma unroll
@@ -332,24 +349,71 @@ struct ManoBwd2Shared {
     float tot[MANO_PART];
     float dRw[MANO_J][9], dtw[MANO_J][3], dJ[MANO_J][3], dRl[MANO_J][9], dpose[48];
     float cR[MANO_J][9], ct[MANO_J][3], cJ[MANO_J][3];     // child -> parent contributions
+    float comps[MANO_J * 45], jsd[MANO_J * 3 * 10];        // m.comps and m.J_shapedirs, staged while the partials travel
 };
+struct ManoRigid;
+__device__ __forceinline__ void mano_rigid_finish(const ManoRigid& mr, const float* r6, const float* tot12, int b);
+#ifdef MANO_PHASES          // phases of the critical workgroup (hm_common.h HM_PH; tools/tail_phases.py)
+static __device__ unsigned long long g_mano_tail[16];
+#define TPH_DECL() HM_PH_DECL()
+#define TPH(k) HM_PH(k)
+#define TPH_FLUSH() HM_PH_FLUSH(g_mano_tail)
+#define TPH_ARG , unsigned long long (&ph_)[15]
+#define TPH_PASS , ph_
+#else
+#define TPH_DECL()
+#define TPH(k)
+#define TPH_FLUSH()
+#define TPH_ARG
+#define TPH_PASS
+#endif
+#define MANO_BWD_THREADS 256        // k_mano_bwd's workgroup: its launch bound AND the block size of both launches
+// Everything the finish reads from memory is requested HERE, in one round trip: both passes over the chunk records (352 sums on
+// 256 threads: the second pass used to wait for the first), the PCA components and the joints' shape directions - which the last
+// lines need and whose addresses never depended on anything (staged in LDS: they used to be a round trip of their own behind the
+// chain) - and the PCA prior's term.  The sums keep their chunk order; PCA, betas and the rigid pose's rot6d backward (r6: the
+// frame's rot6d, in registers since the first half) keep their expressions and run on three waves side by side.
+template <bool RIGID>
 __device__ __forceinline__ void mano_bwd2_body(const ManoModelDev& m, const ManoShared& sh, ManoBwd2Shared& w,
                                                const float* __restrict__ partials, int nchunk, int lb, int b, int pca_dim,
                                                const float* __restrict__ g_pca_extra, float w_extra,
                                                float* __restrict__ g_pca, float* __restrict__ g_rot,
-                                               float* __restrict__ g_betas, float* __restrict__ g_trans)
+                                               float* __restrict__ g_betas, float* __restrict__ g_trans, const ManoRigid& mr,
+                                               const float* r6 TPH_ARG)
 {
-    const int t = threadIdx.x, nt = blockDim.x;
-    for (int k = t; k < MANO_PART; k += nt) {
-        float v[MANO_NCH64];
+    const int t = threadIdx.x, nt = MANO_BWD_THREADS;
+    static_assert(MANO_PART <= 2 * MANO_BWD_THREADS, "two passes over the chunk records");
+    constexpr int NSTAGE = MANO_J * 45 + MANO_J * 3 * 10, SPT = (NSTAGE + MANO_BWD_THREADS - 1) / MANO_BWD_THREADS;
+    const float ex = (g_pca_extra && t < pca_dim) ? g_pca_extra[(long)b * pca_dim + t] : 0.f;
+    {
+        const bool two = t + nt < MANO_PART;
+        float v0[MANO_NCH64], v1[MANO_NCH64], stg[SPT];
 #pragma unroll
-        for (int c = 0; c < MANO_NCH64; ++c)        // all requests first, then the (fixed order) sum
-            v[c] = c < nchunk ? hm_partial_load(partials + ((long)lb * nchunk + c) * MANO_PART + k) : 0.f;
-        float a = 0.f;
+        for (int c = 0; c < MANO_NCH64; ++c) {      // all requests first, then the (fixed order) sums
+            const float* rec = partials + ((long)lb * nchunk + c) * MANO_PART + t;
+            v0[c] = c < nchunk ? hm_partial_load(rec) : 0.f;
+            v1[c] = (two && c < nchunk) ? hm_partial_load(rec + nt) : 0.f;
+        }
 #pragma unroll
-        for (int c = 0; c < MANO_NCH64; ++c) a += v[c];
-        w.tot[k] = a;
+        for (int q = 0; q < SPT; ++q) {
+            const int i = t + q * nt;
+            stg[q] = i < MANO_J * 45 ? m.comps[i] : (i < NSTAGE ? m.J_shapedirs[i - MANO_J * 45] : 0.f);
+        }
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int c = 0; c < MANO_NCH64; ++c) a0 += v0[c];
+#pragma unroll
+        for (int c = 0; c < MANO_NCH64; ++c) a1 += v1[c];
+        w.tot[t] = a0;
+        if (two) w.tot[t + nt] = a1;
+#pragma unroll
+        for (int q = 0; q < SPT; ++q) {
+            const int i = t + q * nt;
+            if (i < MANO_J * 45) w.comps[i] = stg[q];
+            else if (i < NSTAGE) w.jsd[i - MANO_J * 45] = stg[q];
+        }
     }
+    TPH(5);
     int depth = 0, par = -1, maxd = 0;
     if (t < MANO_J) { par = sh.parents[t]; depth = sh.depth[t]; }
 #pragma unroll
@@ -414,6 +478,8 @@ __device__ __forceinline__ void mano_bwd2_body(const ManoModelDev& m, const Mano
         for (int c = 0; c < 3; ++c) w.dJ[t][c] += w.dtw[t][c];
     }
     __syncthreads();
+    TPH(6);
+    // wave 0: Rodrigues backward of the 16 joints; beside it, on waves of their own: the betas (dJ is final) and the rigid pose
     if (t < MANO_J) {
         float dR[9];
 #pragma unroll
@@ -422,8 +488,17 @@ __device__ __forceinline__ void mano_bwd2_body(const ManoModelDev& m, const Mano
         rodrigues_backward(&sh.pose[3 * t], dR, dr);
 #pragma unroll
         for (int c = 0; c < 3; ++c) w.dpose[3 * t + c] = dr[c];
+    } else if (t >= 2 * HM_WAVE && t < 2 * HM_WAVE + 10) {
+        const int l = t - 2 * HM_WAVE;
+        float a = w.tot[192 + 135 + l];
+#pragma unroll
+        for (int q = 0; q < MANO_J * 3; ++q) a += w.jsd[q * 10 + l] * w.dJ[q / 3][q % 3];
+        g_betas[b * 10 + l] = a;
+    } else if (RIGID && t == HM_WAVE) {
+        mano_rigid_finish(mr, r6, &w.tot[340], b);      // the frame's dR (9) and dt (3), summed over the chunks in chunk order above
     }
     __syncthreads();
+    TPH(7);
     if (t < 3) {
         g_rot[b * 3 + t] = w.dpose[t];
         g_trans[b * 3 + t] = w.tot[337 + t];
@@ -431,24 +506,13 @@ __device__ __forceinline__ void mano_bwd2_body(const ManoModelDev& m, const Mano
     for (int i = t; i < pca_dim; i += nt) {
         float a = 0.f;
         if (i < 16) {
-            float cv[45];
 #pragma unroll
-            for (int k = 0; k < 45; ++k) cv[k] = m.comps[i * 45 + k];            // 45 independent loads in flight
-#pragma unroll
-            for (int k = 0; k < 45; ++k) a += cv[k] * w.dpose[3 + k];
+            for (int k = 0; k < 45; ++k) a += w.comps[i * 45 + k] * w.dpose[3 + k];
         }
-        if (g_pca_extra) a += w_extra * g_pca_extra[(long)b * pca_dim + i];      // e.g. the PCA prior's unit gradient
+        if (g_pca_extra) a += w_extra * (i == t ? ex : g_pca_extra[(long)b * pca_dim + i]);      // e.g. the PCA prior's unit gradient
         g_pca[(long)b * pca_dim + i] = a;
     }
-    if (t < 10) {
-        float a = w.tot[192 + 135 + t];
-        float jv[MANO_J * 3];
-#pragma unroll
-        for (int q = 0; q < MANO_J * 3; ++q) jv[q] = m.J_shapedirs[q * 10 + t];
-#pragma unroll
-        for (int q = 0; q < MANO_J * 3; ++q) a += jv[q] * w.dJ[q / 3][q % 3];
-        g_betas[b * 10 + t] = a;
-    }
+    TPH(8);
 }
 
 #ifdef MANO_PHASES
@@ -473,11 +537,21 @@ struct ManoRigid {
     float frame_scale;
     float* g_rot6d; float* g_trans;
 };
+// the fused rigid backward's last step, one thread of the frame's finishing workgroup: tot12 = the frame's dR (9) and dt (3)
+__device__ __forceinline__ void mano_rigid_finish(const ManoRigid& mr, const float* r6, const float* tot12, int b)
+{
+    float dr6[6];
+    rot6d_backward(r6, tot12, dr6);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mr.g_rot6d[(long)b * 6 + k] = dr6[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mr.g_trans[(long)b * 3 + k] = tot12[9 + k];
+}
 // backward: grid (13, B).  First half per (vertex chunk, frame) -> partials (B, 13, MANO_PART); the workgroup that finishes
 // the last chunk of a frame (per-frame ticket) runs the second half for that frame -- one launch, and the chain state is
 // reloaded from the forward (`state`) instead of being recomputed when the caller kept it.
 template <bool RIGID>
-__global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* __restrict__ pca, int pca_stride,
+__global__ __launch_bounds__(MANO_BWD_THREADS) void k_mano_bwd(ManoModelDev m, const float* __restrict__ pca, int pca_stride,
                                                    const float* __restrict__ rot, const float* __restrict__ betas,
                                                    const float* __restrict__ gout, int B, const float* __restrict__ state,
                                                    float* __restrict__ partials, unsigned int* __restrict__ frame_cnt,
@@ -493,7 +567,6 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
     __shared__ float s_g[MANO_VCH][3];
     __shared__ float s_dvp[MANO_VCH * 3];
     __shared__ float s_w[MANO_VCH][MANO_J + 1];
-    __shared__ float red[16];
     __shared__ ManoBwd2Shared w2;
     __shared__ int s_flag;
     // lb: frame of this launch (partials, tickets); b: its row in the caller's arrays (see k_mano_fwd)
@@ -504,6 +577,34 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
     unsigned long long mph_t = wall_clock64();
     if (t == 0) atomicAdd(&g_mano_ph[15], 1ull);
 #endif
+    TPH_DECL();
+    TPH(0);
+    // Requested in front of the chain state, whose round trip they then share: what the vertex stage reads and the state does not
+    // address - the vertex's row of skinning weights (once: it serves the skinning transform and the dA sums), the incoming
+    // gradient (or the rigid backward's mesh vertex and term values) and the frame's rigid pose.
+    const int vq = v0 + (t < nv ? t : 0);
+    const long o = ((long)b * MANO_V + vq) * 3;
+    float4 w4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w4[q] = reinterpret_cast<const float4*>(m.weights + vq * MANO_J)[q];
+    float gin[3] = {0.f, 0.f, 0.f}, mv[3] = {0.f, 0.f, 0.f}, tv[5][3], gfr[3] = {0.f, 0.f, 0.f}, grg[3] = {0.f, 0.f, 0.f};
+    float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rs = 0.f;
+    if (RIGID) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r6[k] = mr.rot6d[(long)b * 6 + k];
+        rs = mr.scale[b / mr.clip_len];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            mv[c] = mr.mesh[o + c];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) tv[k][c] = mr.terms.p[k] ? mr.terms.p[k][o + c] : 0.f;
+            if (mr.g_frame) gfr[c] = mr.g_frame[(long)b * mr.frame_stride + c];
+            if (mr.g_rigid) grg[c] = mr.g_rigid[o + c];
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gin[c] = gout[o + c];
+    }
     if (state) {
         const float* st = state + (long)b * MANO_STATE_DW;
         for (int i = t; i < (int)(sizeof(ManoShared) / 4); i += blockDim.x) reinterpret_cast<float*>(&sh)[i] = st[i];
@@ -514,30 +615,28 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
         mano_posed_chunk(m, sh, v0, s_part, s_vp);
     }
     MPH_MARK(0);
+    TPH(1);
     float g[3] = {0.f, 0.f, 0.f};
-    float racc[12];
+    float racc[15];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) racc[k] = 0.f;
+    for (int k = 0; k < 15; ++k) racc[k] = 0.f;
     if (t < nv) {
-        const int v = v0 + t;
         if (RIGID) {
             // rigid backward of this vertex (the arithmetic of k_rigid_bwd): gf reaches the mesh, gt = gf + the rigid-only terms
-            const long o = ((long)b * MANO_V + v) * 3;
             float R[9];
-            rot6d_to_mat(mr.rot6d + (long)b * 6, R);
-            const float s = mr.scale[b / mr.clip_len];
-            const float mv[3] = {mr.mesh[o], mr.mesh[o + 1], mr.mesh[o + 2]};
+            rot6d_to_mat(r6, R);
+            const float s = rs;
             float gf[3] = {0.f, 0.f, 0.f}, gt[3];
 #pragma unroll
             for (int k = 0; k < 5; ++k)
                 if (mr.terms.p[k]) {
-                    gf[0] += mr.terms.w[k] * mr.terms.p[k][o]; gf[1] += mr.terms.w[k] * mr.terms.p[k][o + 1];
-                    gf[2] += mr.terms.w[k] * mr.terms.p[k][o + 2];
+                    gf[0] += mr.terms.w[k] * tv[k][0]; gf[1] += mr.terms.w[k] * tv[k][1];
+                    gf[2] += mr.terms.w[k] * tv[k][2];
                 }
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                gt[c] = gf[c] + (mr.g_frame ? mr.frame_scale * mr.g_frame[(long)b * mr.frame_stride + c] : 0.f);
-            if (mr.g_rigid) { gt[0] += mr.g_rigid[o]; gt[1] += mr.g_rigid[o + 1]; gt[2] += mr.g_rigid[o + 2]; }
+                gt[c] = gf[c] + (mr.g_frame ? mr.frame_scale * gfr[c] : 0.f);
+            if (mr.g_rigid) { gt[0] += grg[0]; gt[1] += grg[1]; gt[2] += grg[2]; }
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -549,33 +648,45 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
             g[1] = s * (R[3] * gf[0] + R[4] * gf[1] + R[5] * gf[2]);
             g[2] = s * (R[6] * gf[0] + R[7] * gf[1] + R[8] * gf[2]);
         } else {
-            const float* gp = gout + ((long)b * MANO_V + v) * 3;
-            g[0] = gp[0]; g[1] = gp[1]; g[2] = gp[2];
+            g[0] = gin[0]; g[1] = gin[1]; g[2] = gin[2];
         }
     }
     float* out = partials + ((long)lb * gridDim.x + blockIdx.x) * MANO_PART;
-    if (RIGID) {
-        float* red12 = &s_part[0][0][0];          // (>= 16 * 12 floats; the posed-chunk scratch is free by now)
-        hm_block_sum_n<12>(racc, red12);
-        if (t < 12) hm_partial_store(out + 340 + t, racc[t]);
-        __syncthreads();
+    // the chunk's sums of g (d trans) and, fused, the twelve of the rigid backward: ONE pair of barriers (hm_block_sum's tree
+    // per value, so the same floats as three - or twelve and three - reductions one after the other), reduced right where
+    // they are formed: kept live across the skinning stage the rigid sums cost a hundred registers
+    {
+        float* red15 = &s_part[0][0][0];          // (>= 16 * 15 floats; the posed-chunk scratch is free by now)
+        float tg[3] = {g[0], g[1], g[2]};
+        if (RIGID) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) racc[12 + c] = g[c];
+            hm_block_sum_n<15>(racc, red15);
+            float mine = 0.f;
+#pragma unroll
+            for (int k = 0; k < 15; ++k) mine = t == k ? racc[k] : mine;
+            // record layout: 337 .. 339 the sums of g, 340 .. 351 the rigid sums
+            if (t < 15) hm_partial_store(out + (t < 12 ? 340 + t : 337 + (t - 12)), mine);
+        } else {
+            hm_block_sum_n<3>(tg, red15);
+            if (t == 0) { hm_partial_store(out + 337, tg[0]); hm_partial_store(out + 338, tg[1]); hm_partial_store(out + 339, tg[2]); }
+        }
     }
+    MPH_MARK(1);
     if (t < nv) {
-        const int v = v0 + t;
         float T[12];
-        mano_skin_transform(m, sh, v, T);
+        mano_skin_transform_w(sh, w4, T);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             s_g[t][c] = g[c];
             s_dvp[3 * t + c] = T[c] * g[0] + T[4 + c] * g[1] + T[8 + c] * g[2];
         }
-        for (int j = 0; j < MANO_J; ++j) s_w[t][j] = m.weights[v * MANO_J + j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { s_w[t][4 * q] = w4[q].x; s_w[t][4 * q + 1] = w4[q].y; s_w[t][4 * q + 2] = w4[q].z; s_w[t][4 * q + 3] = w4[q].w; }
     }
-    MPH_MARK(1);
-    const float tg0 = hm_block_sum(g[0], red), tg1 = hm_block_sum(g[1], red), tg2 = hm_block_sum(g[2], red);
-    if (t == 0) { hm_partial_store(out + 337, tg0); hm_partial_store(out + 338, tg1); hm_partial_store(out + 339, tg2); }
     __syncthreads();
     MPH_MARK(2);
+    TPH(2);
     // dA[j][r][c] = sum_v W[v][j] g[v][r] [vp;1][c]
     if (t < 192) {
         const int j = t / 12, r = (t % 12) / 4, c = t % 4;
@@ -583,9 +694,9 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
         for (int i = 0; i < nv; ++i) acc += s_w[i][j] * s_g[i][r] * (c < 3 ? s_vp[i][c] : 1.0f);
         hm_partial_store(out + t, acc);
     }
-    __syncthreads();
     MPH_MARK(3);
-    // dfeat[k] = sum_{v,c} M[k][3v+c] dvp[v][c]   (one wave per row, 3 coalesced loads, rows independent)
+    // dfeat[k] = sum_{v,c} M[k][3v+c] dvp[v][c]   (one wave per row, 3 coalesced loads, rows independent; no barrier in front:
+    // the fourth wave has no dA sum and requests its rows at once)
     const int wv = t >> 6, lane = t & 63;
     const int ne = 3 * nv;
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -617,6 +728,7 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     MPH_MARK(4);
+    TPH(3);
     if (t == 0) {
         const unsigned int ticket = atomicAdd(frame_cnt + lb, 1u);
         const int last = ticket == gridDim.x - 1u;
@@ -625,25 +737,17 @@ __global__ __launch_bounds__(256) void k_mano_bwd(ManoModelDev m, const float* _
     }
     __syncthreads();
     MPH_MARK(5);
+    TPH(4);
     if (s_flag) {
-        mano_bwd2_body(m, sh, w2, partials, gridDim.x, lb, b, pca_dim, g_pca_extra, w_extra, g_pca, g_rot, g_betas, g_trans);
-        if (RIGID) {
-            __syncthreads();
-            if (t == 0) {              // the frame's dR (9) and dt (3), summed over the chunks in chunk order by the body above
-                float dr6[6];
-                rot6d_backward(mr.rot6d + (long)b * 6, &w2.tot[340], dr6);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) mr.g_rot6d[(long)b * 6 + k] = dr6[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) mr.g_trans[(long)b * 3 + k] = w2.tot[349 + k];
-            }
-        }
+        mano_bwd2_body<RIGID>(m, sh, w2, partials, gridDim.x, lb, b, pca_dim, g_pca_extra, w_extra, g_pca, g_rot, g_betas, g_trans,
+                              mr, r6 TPH_PASS);
 #ifdef MANO_PHASES
         __syncthreads();
         MPH_MARK(6);
         if (t == 0) atomicAdd(&g_mano_ph[14], 1ull);
 #endif
     }
+    TPH_FLUSH();
 }
 
 extern "C" {
@@ -706,11 +810,11 @@ static int mano_bwd_launch(const void* const* model, const float* pca, int pca_d
     unsigned int* cnt = (unsigned int*)workspace;
     float* partials = (float*)((char*)workspace + 256 + (((size_t)B * 4 + 255) & ~(size_t)255));
     if (mr.mesh)
-        hipLaunchKernelGGL(k_mano_bwd<true>, dim3(MANO_NCH64, B), dim3(256), 0, stream, m, pca, pca_dim, rot, betas,
+        hipLaunchKernelGGL(k_mano_bwd<true>, dim3(MANO_NCH64, B), dim3(MANO_BWD_THREADS), 0, stream, m, pca, pca_dim, rot, betas,
                            g_verts, B, state, partials, cnt, pca_dim, g_pca_extra, w_extra, g_pca, g_rot, g_betas, g_trans, row0,
                            row_stride, mr);
     else
-        hipLaunchKernelGGL(k_mano_bwd<false>, dim3(MANO_NCH64, B), dim3(256), 0, stream, m, pca, pca_dim, rot, betas,
+        hipLaunchKernelGGL(k_mano_bwd<false>, dim3(MANO_NCH64, B), dim3(MANO_BWD_THREADS), 0, stream, m, pca, pca_dim, rot, betas,
                            g_verts, B, state, partials, cnt, pca_dim, g_pca_extra, w_extra, g_pca, g_rot, g_betas, g_trans, row0,
                            row_stride, mr);
     return hm_launch_status();
@@ -762,6 +866,15 @@ int hm_debug_mano_phases(unsigned long long* out)
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mano_ph), sizeof(z));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mano_ph), z, sizeof(z));
+    return HM_OK;
+}
+int hm_debug_tail_mano(unsigned long long* out, int reset)          // k_mano_bwd: 15 phase maxima, first start in [15]
+{
+    unsigned long long z[16] = {0};
+    z[15] = ~0ull;
+    (void)hipDeviceSynchronize();
+    if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mano_tail), sizeof(z));
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mano_tail), z, sizeof(z));
     return HM_OK;
 }
 #endif
